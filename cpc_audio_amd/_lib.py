@@ -15,7 +15,7 @@ DEFAULT_GRU_XCD_LOCAL = 1  # cpc_set_gru_xcd_local: forward hand-over through on
 DEFAULT_GRU_POLL_PLAIN = 15  # cpc_set_gru_poll_plain: every first look of the persistent recurrence through the XCD's L2 (round 6)
 DEFAULT_MFMA_MODE = 3      # what libcpc_hip starts in (cpc_set_mfma_mode): mode 2's arithmetic (two fp16 pieces, 3 MFMAs per
 #                            product) with conv1 / its gradients on the DMA-fed kernels reading H2-stored activations
-EXPECTED_ABI = 15          # cpc_abi_version() of the library these signatures were written for: a stale or variant build that
+EXPECTED_ABI = 16          # cpc_abi_version() of the library these signatures were written for: a stale or variant build that
 #                            exports every symbol with OLDER argument lists would corrupt memory instead of raising -- bind() refuses it
 DEFAULT_DMA_PIPELINE = 2       # cpc_set_dma_pipeline: the tap-pair walk where the shape allows, two 32-k stages elsewhere
 DEFAULT_WGRAD_DMA_STAGES = 4   # cpc_set_wgrad_dma_stages
@@ -114,6 +114,9 @@ SIGNATURES = {
     "cpc_gru_backward_coef": (_I, [_P] * 5 + [_I, _I, _I, _I, _P]),
     "cpc_gru_backward_with_coef": (_I, [_P] * 10 + [_I, _I, _I, _P]),
     "cpc_gru_backward_streams": (_I, [_P] * 10 + [_I, _I, _I, _P, _P]),
+    "cpc_lstm_layout": (_I, [_I, _I, _I, _P]),
+    "cpc_lstm_forward": (_I, [_P] * 9 + [_I, _I, _I, _I, _P]),
+    "cpc_lstm_backward": (_I, [_P] * 10 + [_I, _I, _I, _I, _P]),
     "cpc_nce_layout": (_I, [_I, _I, _I, _I, _P]),
     "cpc_nce_prepare": (_I, [_P] * 6 + [_I, _I, _I, _I, _P]),
     "cpc_nce_forward": (_I, [_P] * 8 + [_I, _I, _I, _I, _P]),

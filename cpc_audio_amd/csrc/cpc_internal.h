@@ -196,6 +196,7 @@ int conv0_backward(const float* wave, const float* w, const float* bias, const f
 int gru_error_flag_fetch(int clear, unsigned* out);
 int nce_error_flag_fetch(int clear, unsigned* out);
 int enc_error_flag_fetch(int clear, unsigned* out);
+int lstm_error_flag_fetch(int clear, unsigned* out);
 
 static inline long align64l(long v) { return (v + 63) & ~63L; }
 

@@ -9,7 +9,7 @@ forward/backward run in the HIP kernels of libcpc_hip.so.
 import torch
 import torch.nn as nn
 
-from .ops import EncoderFunction, GruFunction
+from .ops import EncoderFunction, GruFunction, LstmFunction
 
 
 class ChannelNorm(nn.Module):
@@ -107,12 +107,16 @@ class CPCAR(nn.Module):
     """cpc/model.py:155-204.  For the GRU of the north-star configuration (256 -> 256) baseNet is a torch.nn.GRU used as the
     parameter container (same keys / gate layout) and forward runs cpc_gru_forward (HIP, ``self.hip``).  The reference's other
     autoregressors -- ``LSTM`` (its argparse default, cpc_default_config.py:74), ``RNN``, other widths -- run through baseNet's
-    own torch forward: same semantics incl. the carried hidden state, any device, not the hot path."""
+    own torch forward: same semantics incl. the carried hidden state, any device, not the hot path.
+    ``lstmKernel=True`` (not in the reference's signature; default off) runs the LSTM of 256 -> 256 through cpc_lstm_forward
+    (HIP, ``self.hip_lstm``) for CUDA fp32 input; baseNet stays the nn.LSTM parameter container.  ``self.hip`` keeps meaning
+    the GRU kernel (what the fused train step checks)."""
 
-    def __init__(self, dimEncoded, dimOutput, keepHidden, nLevelsGRU, mode="GRU", reverse=False):
+    def __init__(self, dimEncoded, dimOutput, keepHidden, nLevelsGRU, mode="GRU", reverse=False, lstmKernel=False):
         super().__init__()
         self.RESIDUAL_STD = 0.1
         self.hip = mode not in ("LSTM", "RNN") and dimEncoded == 256 and dimOutput == 256
+        self.hip_lstm = bool(lstmKernel) and mode == "LSTM" and dimEncoded == 256 and dimOutput == 256
         cell = nn.LSTM if mode == "LSTM" else (nn.RNN if mode == "RNN" else nn.GRU)
         self.baseNet = cell(dimEncoded, dimOutput, num_layers=nLevelsGRU, batch_first=True)
         self.hidden = None
@@ -132,6 +136,15 @@ class CPCAR(nn.Module):
         """(B, S, 256) -> (B, S, 256).  In reverse mode the sequence is processed back to front and handed back in its
         original order (cpc/model.py:185-204); the final hidden state is kept for the next call when keepHidden is set."""
         flip = (lambda t: torch.flip(t, [1])) if self.reverse else (lambda t: t)
+        if self.hip_lstm and x.is_cuda and x.dtype == torch.float32:
+            y, hN, cN = LstmFunction.apply(flip(x), self.hidden, False, *self._flat_params())
+            if self.keepHidden:
+                self.hidden = (hN.detach(), cN.detach())
+            out = flip(y)
+            # |h_t| = |o * tanh(c_t)| <= 1 at every step whatever (h0, c0) is: unlike the GRU, whose h_t mixes in h_{t-1},
+            # the output never carries the initial state through, so no check of where self.hidden came from is needed
+            out._cpc_abs_bound = 1.0
+            return out
         if not self.hip:                                       # cpc/model.py:185-204 with baseNet's own torch forward
             y, h = self.baseNet(flip(x), self.hidden)
             if self.keepHidden:

@@ -53,6 +53,9 @@ def check_device_errors(clear=True):
     if mask & 4:
         what.append("a workgroup of the N-split conv forward timed out waiting for its partner's ChannelNorm statistics "
                     "(its rows contain NaN)")
+    if mask & 8:
+        what.append("a workgroup of the persistent LSTM recurrence timed out waiting for its neighbours "
+                    "(outputs contain NaN from that step on)")
     if what:
         raise _lib.CpcHipError("device-side error: " + "; ".join(what))
 
@@ -500,6 +503,57 @@ class GruFunction(torch.autograd.Function):
         _wait(ctx.step, final=False)   # starts the criterion's deferred dz path beside the recurrence just launched, and makes
         #                         this stream wait for it: autograd adds dx to that dz next
         return (dx, None, *grads)
+
+
+class LstmFunction(torch.autograd.Function):
+    """x (B,S,256), state None or (h0, c0) (each (nl,B,256)), 4*nl LSTM parameters -> y (B,S,256), (hN, cN) (each (nl,B,256)).
+
+    The carried state is an input only: neither h0 nor c0 receives a gradient (the reference detaches it between calls,
+    cpc/model.py:194-198), and hN / cN are not differentiable.  per_step: the one-launch-per-step kernels instead of the
+    persistent recurrence (same bits; tests)."""
+
+    @staticmethod
+    def forward(ctx, x, state, per_step, *params):
+        _require_cuda(x, "LstmFunction")
+        lib = _lib.get()
+        B, S, D = x.shape
+        nl = len(params) // 4
+        if D != _HID or params[1].shape != (4 * _HID, _HID):
+            raise NotImplementedError("the HIP LSTM is built for dimEncoded == dimOutput == 256")
+        x = x.contiguous()
+        params = [p.detach().contiguous() for p in params]
+        h0, c0 = (None, None) if state is None else (state[0].detach().contiguous(), state[1].detach().contiguous())
+        flags = 1 if per_step else 0                      # CPC_LSTM_PER_STEP
+        with torch.cuda.device(x.device):
+            sizes = _layout("lstm_layout", lib.cpc_lstm_layout, 3, B, S, nl)
+            saved = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
+            scratch = torch.empty(sizes[1], device=x.device, dtype=torch.float32)
+            y = torch.empty(B, S, _HID, device=x.device, dtype=torch.float32)
+            hN = torch.empty(nl, B, _HID, device=x.device, dtype=torch.float32)
+            cN = torch.empty(nl, B, _HID, device=x.device, dtype=torch.float32)
+            lib.check(lib.cpc_lstm_forward(_p(x), _p(h0), _p(c0), _ptrs(params), _p(saved), _p(scratch), _p(y), _p(hN), _p(cN),
+                                           B, S, nl, flags, _stream()), "lstm_forward")
+        ctx.save_for_backward(x, saved, y, *params)
+        ctx.state = (h0, c0)
+        ctx.dims = (B, S, nl, sizes[2], flags)
+        ctx.mark_non_differentiable(hN, cN)
+        ctx.set_materialize_grads(False)
+        return y, hN, cN
+
+    @staticmethod
+    def backward(ctx, dy, _dhN, _dcN):
+        lib = _lib.get()
+        x, saved, y, *params = ctx.saved_tensors
+        B, S, nl, nscr, flags = ctx.dims
+        h0, c0 = ctx.state
+        dy = torch.zeros_like(y) if dy is None else dy.contiguous()
+        with torch.cuda.device(x.device):
+            scratch = torch.empty(nscr, device=x.device, dtype=torch.float32)
+            dx = torch.empty_like(x)
+            grads = [torch.empty_like(p) for p in params]
+            lib.check(lib.cpc_lstm_backward(_p(x), _p(h0), _p(c0), _ptrs(params), _p(saved), _p(y), _p(dy), _p(scratch), _p(dx),
+                                            _ptrs(grads), B, S, nl, flags, _stream()), "lstm_backward")
+        return (dx, None, None, *grads)
 
 
 def candidate_destinations(ext, B, S, K):

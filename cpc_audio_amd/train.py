@@ -12,15 +12,16 @@ from .optim import Adam
 
 
 def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False, reverse=False, arMode="GRU",
-                sizeWindow=20480, abspos=False, transformerDropout=0.1):
+                sizeWindow=20480, abspos=False, transformerDropout=0.1, lstmKernel=False):
     """cpc/feature_loader.py:124-153 (getEncoder / getAR) + cpc/train.py:311.  arMode 'GRU' (north star) or
-    'transformer' (BASELINE.json config 4: buildTransformerAR(hiddenEncoder, 1, sizeWindow // 160, abspos))."""
+    'transformer' (BASELINE.json config 4: buildTransformerAR(hiddenEncoder, 1, sizeWindow // 160, abspos)); 'LSTM' /
+    'RNN' as the reference (lstmKernel: the LSTM on the HIP kernels, CPCAR)."""
     enc = CPCEncoder(hiddenEncoder, "layerNorm")
     if arMode == "transformer":
         from .transformers import buildTransformerAR
         ar = buildTransformerAR(hiddenEncoder, 1, sizeWindow // 160, abspos, dropout=transformerDropout)
     else:
-        ar = CPCAR(hiddenEncoder, hiddenGar, keepHidden, nLevelsGRU, mode=arMode, reverse=reverse)
+        ar = CPCAR(hiddenEncoder, hiddenGar, keepHidden, nLevelsGRU, mode=arMode, reverse=reverse, lstmKernel=lstmKernel)
     return CPCModel(enc, ar)
 
 

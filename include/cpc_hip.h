@@ -60,12 +60,15 @@ int cpc_get_mfma_mode(void);
  *                                (criterion.py:181-189 draws [0,B) and [1,S)); the index was clamped
  *   CPC_DEVERR_CONV_EXCHANGE     a workgroup of the N-split conv forward (cpc_set_fwd_nsplit) gave up waiting for its partner's
  *                                ChannelNorm statistics; its rows carry NaN
+ *   CPC_DEVERR_LSTM_POLL_TIMEOUT a workgroup of the persistent LSTM recurrence (cpc_lstm_forward / _backward) gave up
+ *                                waiting for another one; its outputs carry NaN from that step on
  * The reference raises Python exceptions for such things; kernels cannot, so the wrapper (ops.check_device_errors) turns
  * the mask into a RuntimeError.  The call synchronises with the device: logging points and tests, not the step path.
  * Returns the mask (>= 0) or a negative number if the flags cannot be read. */
 #define CPC_DEVERR_GRU_POLL_TIMEOUT 1
 #define CPC_DEVERR_NEGATIVE_INDEX 2
 #define CPC_DEVERR_CONV_EXCHANGE 4
+#define CPC_DEVERR_LSTM_POLL_TIMEOUT 8
 int cpc_device_error_flags(int clear);
 
 /* ---------------------------------------------------------------- encoder ----
@@ -286,6 +289,24 @@ int cpc_gru_forward_coef_prepared(const float* x, const float* h0, const float* 
 int cpc_gru_backward_streams(const float* x, const float* h0, const float* const* params, const float* saved,
                              const float* y, const float* dy, const float* coef, float* scratch, float* dx,
                              float* const* grads, int B, int S, int nl, void* stream, void* wgrad_stream);
+
+/* ------------------------------------------------------------ LSTM autoregressor ----
+ * CPCAR with mode "LSTM" (cpc/model.py:167-169, the reference's default --arMode): nn.LSTM(256, 256, num_layers=nl,
+ * batch_first=True), 1 <= nl <= 8, fp32, optional carried state (h0, c0) -- both or neither.
+ * params / grads: weight_ih_l (4H,H), weight_hh_l (4H,H), bias_ih_l, bias_hh_l (4H) for l = 0..nl-1 (torch state-dict order,
+ * gate rows i,f,g,o); grads are OVERWRITTEN.  x, y, dy, dx: (B,S,256); h0, c0, hN, cN: (nl,B,256).
+ * cpc_lstm_layout fills sizes[0..2] = saved / forward-scratch / backward-scratch floats (B * S <= 2^21).
+ * The forward writes `saved` (what the backward reads); y and hN / cN are outputs.  The backward differentiates x and the
+ * parameters; h0 and c0 receive no gradient (the reference detaches the carried state, cpc/model.py:194-198).
+ * flags: CPC_LSTM_PER_STEP runs the per-step kernels (one launch per time step) instead of the persistent recurrence, which is
+ * otherwise taken whenever its grid can be resident at once; both give the same bits.  Arguments are checked before any launch. */
+#define CPC_LSTM_PER_STEP 1
+int cpc_lstm_layout(int B, int S, int nl, long* sizes);
+int cpc_lstm_forward(const float* x, const float* h0, const float* c0, const float* const* params, float* saved,
+                     float* scratch, float* y, float* hN, float* cN, int B, int S, int nl, int flags, void* stream);
+int cpc_lstm_backward(const float* x, const float* h0, const float* c0, const float* const* params, const float* saved,
+                      const float* y, const float* dy, float* scratch, float* dx, float* const* grads, int B, int S, int nl,
+                      int flags, void* stream);
 
 /* ---------------------------------------------------------------- transformer layer ----
  * One TransformerLayer of cpc/transformers.py:103-111 (buildTransformerAR, :130-139), d_model 256, 8 heads,
