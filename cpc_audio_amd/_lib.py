@@ -117,6 +117,11 @@ SIGNATURES = {
     "cpc_lstm_layout": (_I, [_I, _I, _I, _P]),
     "cpc_lstm_forward": (_I, [_P] * 9 + [_I, _I, _I, _I, _P]),
     "cpc_lstm_backward": (_I, [_P] * 10 + [_I, _I, _I, _I, _P]),
+    "cpc_supervised_layout": (_I, [_I, _I, _I, _I, _P]),
+    "cpc_classifier_forward": (_I, [_P, _L] + [_P] * 6 + [_I, _I, _P]),
+    "cpc_classifier_backward": (_I, [_P, _L] + [_P] * 9 + [_I, _I, _P]),
+    "cpc_ctc_forward": (_I, [_P] * 6 + [_I, _I, _I, _P]),
+    "cpc_ctc_backward": (_I, [_P] * 3 + [_I, _I, _I, _P]),
     "cpc_nce_layout": (_I, [_I, _I, _I, _I, _P]),
     "cpc_nce_prepare": (_I, [_P] * 6 + [_I, _I, _I, _I, _P]),
     "cpc_nce_forward": (_I, [_P] * 8 + [_I, _I, _I, _I, _P]),

@@ -10,7 +10,9 @@ import math
 import torch
 import torch.nn as nn
 
-from .ops import InfoNCEFunction, InfoNCEScoresFunction, prepare_negatives
+import torch.nn.functional as F
+
+from .ops import ClassifierXentFunction, CtcXentFunction, InfoNCEFunction, InfoNCEScoresFunction, prepare_negatives
 
 _HEAD_TILE = 16          # prediction heads per call of the score kernels (a wavefront's MFMA tile; ops.head_group walks more)
 
@@ -393,3 +395,139 @@ class CPCUnsupersivedCriterion(BaseCriterion):
             losses.append(l)
             accs.append(a)
         return torch.cat(losses).view(1, -1), torch.cat(accs).view(1, -1)
+
+
+# --------------------------------------------------------------------------- supervised criteria
+# cpc/criterion/criterion.py:128-367: what linear-separability evaluation (cpc/eval/linear_separability.py) and
+# train.py --supervised train on top of CPC features.  With 256 input features and one linear layer the loss, the accuracy and
+# every gradient run in csrc/supervised.hip (ops.ClassifierXentFunction / ops.CtcXentFunction: CUDA fp32 only, CPU tensors
+# raise); other widths and nLayers > 1 run on the modules' own torch ops (``hip_path`` is False), as the reference does.
+
+def _on_hip(layer, dim):
+    return dim == 256 and isinstance(layer, nn.Linear)
+
+
+class NoneCriterion(BaseCriterion):
+    """cpc/criterion/criterion.py:130-136."""
+
+    def forward(self, cFeature, encodedData, label):
+        return torch.zeros(1, 1, device=cFeature.device), torch.zeros(1, 1, device=cFeature.device)
+
+
+class SpeakerCriterion(BaseCriterion):
+    """cpc/criterion/criterion.py:182-203: a linear classifier of the last frame's context vector."""
+
+    def __init__(self, dimEncoder, nSpeakers):
+        super().__init__()
+        self.linearSpeakerClassifier = nn.Linear(dimEncoder, nSpeakers)
+        self.lossCriterion = nn.CrossEntropyLoss()
+        self.entropyCriterion = nn.LogSoftmax(dim=1)
+        self.hip_path = _on_hip(self.linearSpeakerClassifier, dimEncoder)
+
+    def forward(self, cFeature, otherEncoded, label):
+        batchSize = cFeature.size(0)
+        last = cFeature[:, -1, :]                              # read in place by the kernel (row stride S * 256)
+        lin = self.linearSpeakerClassifier
+        if self.hip_path:
+            return ClassifierXentFunction.apply(last, label, lin.weight, lin.bias)
+        predictions = lin(last.reshape(batchSize, -1))
+        loss = self.lossCriterion(predictions, label).view(1, -1)
+        acc = (predictions.max(1)[1] == label).double().mean().view(1, -1)
+        return loss, acc
+
+
+class PhoneCriterion(BaseCriterion):
+    """cpc/criterion/criterion.py:206-246: a per-frame classifier of the context vectors (or of the encoder's output when
+    ``onEncoder``); nLayers > 1 stacks Linear / ReLU / Linear (nPhones wide) and runs on torch."""
+
+    def __init__(self, dimEncoder, nPhones, onEncoder, nLayers=1):
+        super().__init__()
+        if nLayers == 1:
+            self.PhoneCriterionClassifier = nn.Linear(dimEncoder, nPhones)
+        else:
+            outLayers = [nn.Linear(dimEncoder, nPhones)]
+            for _ in range(nLayers - 1):
+                outLayers.append(nn.ReLU())
+                outLayers.append(nn.Linear(nPhones, nPhones))
+            self.PhoneCriterionClassifier = nn.Sequential(*outLayers)
+        self.lossCriterion = nn.CrossEntropyLoss()
+        self.onEncoder = onEncoder
+        self.hip_path = _on_hip(self.PhoneCriterionClassifier, dimEncoder)
+
+    def forward(self, cFeature, otherEncoded, label):
+        features = otherEncoded if self.onEncoder else cFeature
+        B, S = features.size(0), features.size(1)
+        if label.dim() != 2 or tuple(label.shape) != (B, S):
+            raise ValueError(f"PhoneCriterion: per-frame labels of shape ({B}, {S}) expected, got {tuple(label.shape)}")
+        if self.hip_path:
+            lin = self.PhoneCriterionClassifier
+            return ClassifierXentFunction.apply(features.reshape(B * S, -1), label.reshape(-1), lin.weight, lin.bias)
+        predictions = self.getPrediction(features)
+        predictions = predictions.view(-1, predictions.size(2))
+        label = label.view(-1)
+        loss = self.lossCriterion(predictions, label).view(1, -1)
+        acc = (predictions.max(1)[1] == label).double().mean().view(1, -1)
+        return loss, acc
+
+    def getPrediction(self, cFeature):
+        batchSize, seqSize = cFeature.size(0), cFeature.size(1)
+        cFeature = cFeature.contiguous().view(batchSize * seqSize, -1)
+        output = self.PhoneCriterionClassifier(cFeature)
+        return output.view(batchSize, seqSize, -1)
+
+
+def collapse_label_chain(labels):
+    """cpc/criterion/seq_alignment.py:64-86 without the host round trip: (B, S) frame labels -> (the collapsed labels of all
+    sequences one behind the other, their lengths (B,)) -- position 0 and every position whose label differs from the one
+    before.  The HIP path collapses inside the kernel; this serves the torch path."""
+    keep = torch.ones_like(labels, dtype=torch.bool)
+    keep[:, 1:] = labels[:, 1:] != labels[:, :-1]
+    return labels[keep], keep.sum(dim=1)
+
+
+class CTCPhoneCriterion(BaseCriterion):
+    """cpc/criterion/criterion.py:249-283: a per-frame classifier with one extra (blank) class trained with nn.CTCLoss on the
+    collapsed frame labels; the second output is zeros(1, 1), as in the reference."""
+
+    def __init__(self, dimEncoder, nPhones, onEncoder):
+        super().__init__()
+        self.PhoneCriterionClassifier = nn.Linear(dimEncoder, nPhones + 1)
+        self.lossCriterion = nn.CTCLoss(blank=nPhones, zero_infinity=True)
+        self.onEncoder = onEncoder
+        if onEncoder:
+            raise ValueError("On encoder version not implemented yet")
+        self.BLANK_LABEL = nPhones
+        self.hip_path = _on_hip(self.PhoneCriterionClassifier, dimEncoder)
+
+    def getPrediction(self, cFeature):
+        B, S, H = cFeature.size()
+        cFeature = cFeature.contiguous().view(B * S, H)
+        return self.PhoneCriterionClassifier(cFeature).view(B, S, -1)
+
+    def forward(self, cFeature, otherEncoded, label):
+        B, S, H = cFeature.size()
+        if label.dim() != 2 or tuple(label.shape) != (B, S):
+            raise ValueError(f"CTCPhoneCriterion: per-frame labels of shape ({B}, {S}) expected, got {tuple(label.shape)}")
+        if self.hip_path:
+            lin = self.PhoneCriterionClassifier
+            loss = CtcXentFunction.apply(cFeature, label, lin.weight, lin.bias)
+            return loss, torch.zeros(1, 1, device=loss.device)
+        predictions = F.log_softmax(self.getPrediction(cFeature), dim=2).permute(1, 0, 2)
+        targets, sizes = collapse_label_chain(label.to(predictions.device))
+        inputSizes = torch.full((B,), S, dtype=torch.int64, device=predictions.device)
+        loss = self.lossCriterion(predictions, targets, inputSizes, sizes).view(1, -1)
+        return loss, torch.zeros(1, 1, device=loss.device)
+
+
+class ModelCriterionCombined(torch.nn.Module):
+    """cpc/criterion/criterion.py:358-367."""
+
+    def __init__(self, model, criterion):
+        super().__init__()
+        self.model = model
+        self.criterion = criterion
+
+    def forward(self, data, label):
+        c_feature, encoded_data, label = self.model(data, label)
+        loss, acc = self.criterion(c_feature, encoded_data, label)
+        return loss, acc

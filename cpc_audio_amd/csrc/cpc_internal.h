@@ -197,6 +197,7 @@ int gru_error_flag_fetch(int clear, unsigned* out);
 int nce_error_flag_fetch(int clear, unsigned* out);
 int enc_error_flag_fetch(int clear, unsigned* out);
 int lstm_error_flag_fetch(int clear, unsigned* out);
+int sup_error_flag_fetch(int clear, unsigned* out);
 
 static inline long align64l(long v) { return (v + 63) & ~63L; }
 

@@ -56,6 +56,8 @@ def check_device_errors(clear=True):
     if mask & 8:
         what.append("a workgroup of the persistent LSTM recurrence timed out waiting for its neighbours "
                     "(outputs contain NaN from that step on)")
+    if mask & 16:
+        what.append("a supervised criterion received a label outside its class range (it was clamped; the loss is NaN)")
     if what:
         raise _lib.CpcHipError("device-side error: " + "; ".join(what))
 
@@ -554,6 +556,117 @@ class LstmFunction(torch.autograd.Function):
             lib.check(lib.cpc_lstm_backward(_p(x), _p(h0), _p(c0), _ptrs(params), _p(saved), _p(y), _p(dy), _p(scratch), _p(dx),
                                             _ptrs(grads), B, S, nl, flags, _stream()), "lstm_backward")
         return (dx, None, None, *grads)
+
+
+CTC_MAX_SEQ = 512        # cpc_ctc_forward: longest sequence (frames) the one-workgroup recursion holds in LDS
+
+
+def _labels_on(label, device):
+    label = label.to(device, non_blocking=True)
+    return (label if label.dtype == torch.int64 else label.to(torch.int64)).contiguous()
+
+
+def _rows_of(x, what):
+    """(R, 256) features with unit column stride: their row stride (cFeature[:, -1, :] is read in place)."""
+    if x.dim() != 2 or x.shape[1] != _HID:
+        raise NotImplementedError(f"cpc_audio_amd.{what}: the HIP classifier is built for 256 input features")
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < _HID):
+        x = x.contiguous()
+    return x, max(int(x.stride(0)), _HID)
+
+
+def _classifier_backward(x, ldx, weight, label, saved, dloss, dlogits, R, C, need_dx):
+    lib = _lib.get()
+    sizes = _layout("supervised_layout", lib.cpc_supervised_layout, 3, R, 1, C, 0)
+    scratch = torch.empty(sizes[1], device=x.device, dtype=torch.float32)
+    dW, db = torch.empty_like(weight), torch.empty(C, device=x.device, dtype=torch.float32)
+    dx = torch.empty(R, _HID, device=x.device, dtype=torch.float32) if need_dx else None
+    lib.check(lib.cpc_classifier_backward(x.data_ptr(), ldx, _p(weight), _p(label), _p(saved), _p(dloss), _p(dlogits),
+                                          _p(scratch), _p(dW), _p(db), _p(dx), R, C, _stream()), "classifier_backward")
+    return dx, dW, db
+
+
+class ClassifierXentFunction(torch.autograd.Function):
+    """x (R,256) (any row stride), label (R,) int64, weight (C,256), bias (C,) -> loss (1,1) float32, acc (1,1) float64:
+    nn.Linear + nn.CrossEntropyLoss() and (argmax == label).double().mean() (cpc/criterion/criterion.py:198-203, 226-231).
+    acc is not differentiable; x receives a gradient only when it requires one."""
+
+    @staticmethod
+    def forward(ctx, x, label, weight, bias):
+        _require_cuda(x, "ClassifierXentFunction")
+        lib = _lib.get()
+        x, ldx = _rows_of(x, "ClassifierXentFunction")
+        R, C = x.shape[0], weight.shape[0]
+        label = _labels_on(label, x.device).view(-1)
+        if label.numel() != R:
+            raise ValueError(f"ClassifierXentFunction: {label.numel()} labels for {R} feature rows")
+        weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
+        with torch.cuda.device(x.device):
+            sizes = _layout("supervised_layout", lib.cpc_supervised_layout, 3, R, 1, C, 0)
+            saved = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
+            loss = torch.empty(1, 1, device=x.device, dtype=torch.float32)
+            acc = torch.empty(1, 1, device=x.device, dtype=torch.float64)
+            lib.check(lib.cpc_classifier_forward(x.data_ptr(), ldx, _p(weight), _p(bias), _p(label), _p(saved), _p(loss),
+                                                 _p(acc), R, C, _stream()), "classifier_forward")
+        ctx.save_for_backward(x, label, weight, saved)
+        ctx.dims = (ldx, R, C)
+        ctx.mark_non_differentiable(acc)
+        return loss, acc
+
+    @staticmethod
+    def backward(ctx, dloss, _dacc):
+        x, label, weight, saved = ctx.saved_tensors
+        ldx, R, C = ctx.dims
+        if dloss is None:
+            return None, None, None, None
+        with torch.cuda.device(x.device):
+            dx, dW, db = _classifier_backward(x, ldx, weight, label, saved, dloss.contiguous(), None, R, C,
+                                              ctx.needs_input_grad[0])
+        return dx, None, dW, db
+
+
+class CtcXentFunction(torch.autograd.Function):
+    """x (B,S,256), label (B,S) int64 frame labels, weight (C,256), bias (C,) -> loss (1,1) float32: nn.Linear, log_softmax
+    and nn.CTCLoss(blank=C-1, zero_infinity=True) on the collapsed labels with every input length S
+    (cpc/criterion/criterion.py:265-283), 1 <= S <= CTC_MAX_SEQ."""
+
+    @staticmethod
+    def forward(ctx, x, label, weight, bias):
+        _require_cuda(x, "CtcXentFunction")
+        lib = _lib.get()
+        if x.dim() != 3 or x.shape[2] != _HID:
+            raise NotImplementedError("cpc_audio_amd.CtcXentFunction: the HIP classifier is built for 256 input features")
+        B, S, _ = x.shape
+        C = weight.shape[0]
+        if S > CTC_MAX_SEQ:
+            raise ValueError(f"CtcXentFunction: sequences of at most {CTC_MAX_SEQ} frames are supported (got {S})")
+        label = _labels_on(label, x.device)
+        if tuple(label.shape) != (B, S):
+            raise ValueError(f"CtcXentFunction: labels of shape {tuple(label.shape)} for features of shape {tuple(x.shape)}")
+        x = x.contiguous()
+        weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
+        with torch.cuda.device(x.device):
+            sizes = _layout("supervised_layout", lib.cpc_supervised_layout, 3, B, S, C, 1)
+            saved = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
+            loss = torch.empty(1, 1, device=x.device, dtype=torch.float32)
+            lib.check(lib.cpc_ctc_forward(_p(x), _p(weight), _p(bias), _p(label), _p(saved), _p(loss), B, S, C, _stream()),
+                      "ctc_forward")
+        ctx.save_for_backward(x, weight, saved)
+        ctx.dims = (B, S, C, sizes[2])
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        x, weight, saved = ctx.saved_tensors
+        B, S, C, ndl = ctx.dims
+        if dloss is None:
+            return None, None, None, None
+        lib = _lib.get()
+        with torch.cuda.device(x.device):
+            dlogits = torch.empty(ndl, device=x.device, dtype=torch.float32)
+            lib.check(lib.cpc_ctc_backward(_p(saved), _p(dloss.contiguous()), _p(dlogits), B, S, C, _stream()), "ctc_backward")
+            dx, dW, db = _classifier_backward(x, _HID, weight, None, None, None, dlogits, B * S, C, ctx.needs_input_grad[0])
+        return (None if dx is None else dx.view(B, S, _HID)), None, dW, db
 
 
 def candidate_destinations(ext, B, S, K):

@@ -62,6 +62,8 @@ int cpc_get_mfma_mode(void);
  *                                ChannelNorm statistics; its rows carry NaN
  *   CPC_DEVERR_LSTM_POLL_TIMEOUT a workgroup of the persistent LSTM recurrence (cpc_lstm_forward / _backward) gave up
  *                                waiting for another one; its outputs carry NaN from that step on
+ *   CPC_DEVERR_LABEL_RANGE       a supervised criterion (cpc_classifier_forward, cpc_ctc_forward) met a label outside [0, C)
+ *                                (CTC: [0, C-1)); it was clamped for addressing and the loss is NaN
  * The reference raises Python exceptions for such things; kernels cannot, so the wrapper (ops.check_device_errors) turns
  * the mask into a RuntimeError.  The call synchronises with the device: logging points and tests, not the step path.
  * Returns the mask (>= 0) or a negative number if the flags cannot be read. */
@@ -69,6 +71,7 @@ int cpc_get_mfma_mode(void);
 #define CPC_DEVERR_NEGATIVE_INDEX 2
 #define CPC_DEVERR_CONV_EXCHANGE 4
 #define CPC_DEVERR_LSTM_POLL_TIMEOUT 8
+#define CPC_DEVERR_LABEL_RANGE 16
 int cpc_device_error_flags(int clear);
 
 /* ---------------------------------------------------------------- encoder ----
@@ -307,6 +310,35 @@ int cpc_lstm_forward(const float* x, const float* h0, const float* c0, const flo
 int cpc_lstm_backward(const float* x, const float* h0, const float* c0, const float* const* params, const float* saved,
                       const float* y, const float* dy, float* scratch, float* dx, float* const* grads, int B, int S, int nl,
                       int flags, void* stream);
+
+/* ------------------------------------------------------------ supervised criteria ----
+ * SpeakerCriterion / PhoneCriterion (cpc/criterion/criterion.py:182-246): nn.Linear(256, C) + nn.CrossEntropyLoss() (mean)
+ * and (argmax == label).double().mean(); CTCPhoneCriterion (criterion.py:249-283): the same linear layer, log_softmax and
+ * nn.CTCLoss(blank = C-1, zero_infinity = True, reduction mean) with every input length S and the frame labels collapsed
+ * in the kernel (collapseLabelChain, cpc/criterion/seq_alignment.py:64-86: no host round trip).  fp32, 2 <= C <= 8192.
+ * cpc_supervised_layout(B, S, C, ctc, sizes): R = B * S rows (the speaker criterion: B rows, S = 1), R * C < 2^31, CTC with
+ *   1 <= S <= 512.  sizes[0] = saved floats (what the forward writes for the backward: logits, per-row log-sum-exp, ...),
+ *   sizes[1] = scratch floats of cpc_classifier_backward (dlogits and per-slab dW / db partials), sizes[2] = dlogits floats of
+ *   cpc_ctc_backward (R * C; 0 without ctc).
+ * x: R rows of 256 floats, row r at x + r * ldx (ldx >= 256: cFeature[:, -1, :] read in place); W (C,256), b (C);
+ * labels: int64, (R) / (B,S).  A label out of range is clamped for addressing, raises CPC_DEVERR_LABEL_RANGE and makes the
+ * loss NaN.  loss: one float; acc: one double.  Arguments are checked before any launch; nothing is allocated and nothing
+ * waits for the device.
+ * cpc_classifier_backward: dW, db overwritten; dX (R,256 dense) only when non-NULL.  dlogits NULL: g (softmax - onehot) / R
+ * from the saved forward (labels, saved and dloss -- one device float, the loss's gradient -- required); non-NULL: the
+ * caller's (R,C) dlogits (the CTC path; labels, saved and dloss ignored).  dW / db are summed over row slabs in a fixed order
+ * (no float atomics: the same bits on every run).
+ * cpc_ctc_backward: dlogits (B*S, C) of the loss w.r.t. the logits, scaled by *dloss (zero for a sequence whose loss was
+ * infinite); W, b and x then receive their gradients through cpc_classifier_backward(dlogits = ...). */
+int cpc_supervised_layout(int B, int S, int C, int ctc, long* sizes);
+int cpc_classifier_forward(const float* x, long ldx, const float* W, const float* b, const long long* labels, float* saved,
+                           float* loss, double* acc, int R, int C, void* stream);
+int cpc_classifier_backward(const float* x, long ldx, const float* W, const long long* labels, const float* saved,
+                            const float* dloss, const float* dlogits, float* scratch, float* dW, float* db, float* dX, int R,
+                            int C, void* stream);
+int cpc_ctc_forward(const float* x, const float* W, const float* b, const long long* labels, float* saved, float* loss, int B,
+                    int S, int C, void* stream);
+int cpc_ctc_backward(const float* saved, const float* dloss, float* dlogits, int B, int S, int C, void* stream);
 
 /* ---------------------------------------------------------------- transformer layer ----
  * One TransformerLayer of cpc/transformers.py:103-111 (buildTransformerAR, :130-139), d_model 256, 8 heads,

@@ -1,0 +1,246 @@
+"""Supervised-criterion kernels (csrc/supervised.hip) on the host SIMT emulator against torch in float64 on the CPU: the
+linear classifier with cross-entropy of SpeakerCriterion / PhoneCriterion and the CTC loss of CTCPhoneCriterion
+(cpc/criterion/criterion.py:182-283)."""
+import ctypes
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from emu_util import P, emu, rel_err
+from supervised_util import frame_labels
+
+H = 256
+LABEL_RANGE = 16     # CPC_DEVERR_LABEL_RANGE
+
+
+def _layout(lib, B, S, C, ctc):
+    sizes = (ctypes.c_long * 3)()
+    assert lib.cpc_supervised_layout(B, S, C, ctc, sizes) == 0
+    return tuple(sizes)
+
+
+def _classifier(lib, x, ldx, W, b, y, dlogits=None, need_dx=True, canary=0):
+    """Forward + backward (dloss = 1) through the C ABI; every output buffer carries `canary` spare floats behind its size."""
+    R, C = y.numel() if dlogits is None else dlogits.shape[0], W.shape[0]
+    saved_n, scr_n, _ = _layout(lib, R, 1, C, 0)
+    saved = torch.full((saved_n + canary,), float("nan"))
+    scratch = torch.full((scr_n + canary,), float("nan"))
+    loss = torch.full((1 + canary,), 7.0)
+    acc = torch.full((1 + canary,), 7.0, dtype=torch.float64)
+    dloss = torch.ones(1)
+    if dlogits is None:
+        assert lib.cpc_classifier_forward(x.data_ptr(), ldx, P(W), P(b), P(y), P(saved), P(loss), P(acc), R, C, None) == 0
+    dW = torch.full((C * H + canary,), 7.0)
+    db = torch.full((C + canary,), 7.0)
+    dX = torch.full((R * H + canary,), 7.0) if need_dx else None
+    assert lib.cpc_classifier_backward(x.data_ptr(), ldx, P(W), P(y), P(saved), P(dloss), P(dlogits), P(scratch), P(dW), P(db),
+                                       P(dX), R, C, None) == 0
+    out = dict(loss=loss, acc=acc, dW=dW, db=db, dX=dX, saved=saved, scratch=scratch)
+    return out
+
+
+def _oracle_xent(x, W, b, y):
+    xr, Wr, br = (t.double().clone().requires_grad_(True) for t in (x, W, b))
+    logits = F.linear(xr, Wr, br)
+    loss = F.cross_entropy(logits, y)
+    loss.backward()
+    return loss.detach(), logits.detach(), Wr.grad, br.grad, xr.grad
+
+
+def _check_acc(acc, logits, y):
+    """Exactly the float64 accuracy, except that rows whose top-2 margin is under 1e-5 of the row's scale may differ (counted)."""
+    top2 = logits.topk(2, dim=1).values
+    scale = logits.abs().max(dim=1).values.clamp_min(1e-30)
+    close = (top2[:, 0] - top2[:, 1]) < 1e-5 * scale
+    hit = (logits.argmax(dim=1) == y)
+    lo = (hit & ~close).sum().item() / y.numel()
+    hi = (hit | close).sum().item() / y.numel()
+    assert lo - 1e-15 <= acc <= hi + 1e-15, (acc, lo, hi, int(close.sum()))
+    if not close.any():
+        assert acc == hit.double().mean().item()
+    return int(close.sum())
+
+
+def _case(R, C, seed, dim_scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(R, H, generator=g) * dim_scale
+    W = 0.1 * torch.randn(C, H, generator=g)
+    b = 0.1 * torch.randn(C, generator=g)
+    y = torch.randint(0, C, (R,), generator=g)
+    return x, W, b, y
+
+
+@pytest.mark.parametrize("R,C", [(512, 41), (300, 300), (77, 2), (1, 5)])
+def test_classifier_matches_torch_float64_emulated(R, C):
+    lib = emu()
+    x, W, b, y = _case(R, C, seed=R + C)
+    out = _classifier(lib, x, H, W, b, y)
+    loss, logits, dW, db, dx = _oracle_xent(x, W, b, y)
+    assert abs(out["loss"][0].item() - loss.item()) <= 1e-5 * abs(loss.item())
+    _check_acc(out["acc"][0].item(), logits, y)
+    assert rel_err(out["dW"].double().view(C, H), dW) < 1e-5
+    assert rel_err(out["db"].double(), db) < 1e-5
+    assert rel_err(out["dX"].double().view(R, H), dx) < 1e-5
+    assert lib.cpc_device_error_flags(1) == 0
+
+
+def test_classifier_reads_the_last_frame_through_its_row_stride_emulated():
+    """SpeakerCriterion: cFeature[:, -1, :] read in place (row stride S * 256), no dX requested (frozen features)."""
+    lib = emu()
+    Bq, S, C = 6, 9, 12
+    g = torch.Generator().manual_seed(3)
+    c = torch.randn(Bq, S, H, generator=g)
+    W, b = 0.1 * torch.randn(C, H, generator=g), 0.1 * torch.randn(C, generator=g)
+    y = torch.randint(0, C, (Bq,), generator=g)
+    last = c[:, -1, :]
+    assert last.stride(0) == S * H
+    out = _classifier(lib, last, S * H, W, b, y, need_dx=False)
+    loss, logits, dW, db, _ = _oracle_xent(last.contiguous(), W, b, y)
+    assert abs(out["loss"][0].item() - loss.item()) <= 1e-5 * abs(loss.item())
+    _check_acc(out["acc"][0].item(), logits, y)
+    assert rel_err(out["dW"].double().view(C, H), dW) < 1e-5 and rel_err(out["db"].double(), db) < 1e-5
+
+
+def test_argmax_ties_break_on_the_first_index_emulated():
+    lib = emu()
+    R, C = 8, 70
+    x = torch.zeros(R, H)
+    W = torch.zeros(C, H)
+    b = torch.zeros(C)
+    b[5] = b[66] = 1.0                                   # tie between class 5 and class 66 (another 64-class tile)
+    y = torch.tensor([5, 66, 5, 66, 0, 5, 66, 5])
+    out = _classifier(lib, x, H, W, b, y)
+    assert out["acc"][0].item() == 4 / 8                 # torch.max picks 5
+
+
+def _ctc_oracle(x, W, b, labels, dtype=torch.float64):
+    xr, Wr, br = (t.to(dtype).clone().requires_grad_(True) for t in (x, W, b))
+    Bq, S, _ = x.shape
+    logits = F.linear(xr, Wr, br)
+    logits.retain_grad()
+    lp = F.log_softmax(logits, dim=2).permute(1, 0, 2)
+    keep = torch.ones_like(labels, dtype=torch.bool)
+    keep[:, 1:] = labels[:, 1:] != labels[:, :-1]
+    loss = F.ctc_loss(lp, labels[keep], torch.full((Bq,), S, dtype=torch.long), keep.sum(1), blank=W.shape[0] - 1,
+                      reduction="mean", zero_infinity=True)
+    loss.backward()
+    return loss.detach(), logits.grad.reshape(Bq * S, -1), Wr.grad, br.grad, xr.grad
+
+
+def _ctc(lib, x, W, b, labels, canary=0):
+    Bq, S, _ = x.shape
+    C = W.shape[0]
+    saved_n, _, dl_n = _layout(lib, Bq, S, C, 1)
+    saved = torch.full((saved_n + canary,), float("nan"))
+    loss = torch.full((1 + canary,), 7.0)
+    assert lib.cpc_ctc_forward(P(x), P(W), P(b), P(labels), P(saved), P(loss), Bq, S, C, None) == 0
+    dl = torch.full((dl_n + canary,), 7.0)
+    assert lib.cpc_ctc_backward(P(saved), P(torch.ones(1)), P(dl), Bq, S, C, None) == 0
+    out = _classifier(lib, x.view(Bq * S, H), H, W, b, None, dlogits=dl[:dl_n].view(Bq * S, C), canary=canary)
+    return loss, dl, out, saved
+
+
+def _ctc_inputs(seed, Bq=4, S=128, n_phones=41):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(Bq, S, H, generator=g)
+    W = 0.1 * torch.randn(n_phones + 1, H, generator=g)
+    b = 0.1 * torch.randn(n_phones + 1, generator=g)
+    return x, W, b, frame_labels(n_phones, Bq, S, seed=seed)
+
+
+def test_ctc_matches_torch_float64_emulated():
+    """S = 128 with runs of varied length, long runs, a sequence with nothing to collapse (L = S) and random runs."""
+    lib = emu()
+    x, W, b, labels = _ctc_inputs(11)
+    loss, dl, out, _ = _ctc(lib, x, W, b, labels)
+    rl, rdl, rdW, rdb, rdx = _ctc_oracle(x, W, b, labels)
+    assert abs(loss[0].item() - rl.item()) <= 1e-5 * abs(rl.item())
+    assert rel_err(dl.double().view_as(rdl), rdl) < 1e-4
+    assert rel_err(out["dW"].double().view_as(rdW), rdW) < 1e-4
+    assert rel_err(out["db"].double(), rdb) < 1e-4
+    assert rel_err(out["dX"].double().view_as(rdx), rdx) < 1e-4
+    assert lib.cpc_device_error_flags(1) == 0
+
+
+def test_ctc_zero_infinity_emulated():
+    """A sequence whose every alignment has probability 0 in float (one of its labels has a logit of -inf, so alpha
+    underflows to -inf): its loss counts 0 and its gradient is 0, as in nn.CTCLoss(zero_infinity=True); the other sequence is
+    untouched and the mean still divides by both."""
+    lib = emu()
+    x, W, b, labels = _ctc_inputs(12, Bq=2, S=64)
+    k = next(c for c in range(41) if not (labels[0] == c).any())
+    labels[1, 30:33] = k
+    b[k] = float("-inf")
+    loss, dl, out, _ = _ctc(lib, x, W, b, labels)
+    # oracle: sequence 0 alone (it does not contain k; a bias of -1e4 is exp-underflow in float64 too), halved
+    b0 = b.clone()
+    b0[k] = -1e4
+    rl, rdl, rdW, rdb, rdx = _ctc_oracle(x[:1], W, b0, labels[:1])
+    assert abs(loss[0].item() - rl.item() / 2) <= 1e-5 * abs(rl.item() / 2)
+    dlv = dl.view(2, 64, -1)
+    assert bool((dlv[1] == 0).all())
+    assert rel_err(dlv[0].double(), rdl / 2) < 1e-4
+    assert rel_err(out["dW"].double().view_as(rdW), rdW / 2) < 1e-4 and rel_err(out["db"].double(), rdb / 2) < 1e-4
+    dX = out["dX"].double().view(2, 64, H)
+    assert rel_err(dX[0], rdx[0] / 2) < 1e-4 and bool((dX[1] == 0).all())
+
+
+def test_label_out_of_range_flags_and_gives_nan_emulated():
+    lib = emu()
+    lib.cpc_device_error_flags(1)
+    canary = 64
+    x, W, b, y = _case(40, 41, seed=9)
+    y[7] = 41
+    out = _classifier(lib, x, H, W, b, y, canary=canary)
+    assert torch.isnan(out["loss"][0])
+    assert lib.cpc_device_error_flags(1) == LABEL_RANGE
+    for k, n in (("loss", 1), ("acc", 1), ("dW", 41 * H), ("db", 41), ("dX", 40 * H)):
+        assert bool((out[k][n:] == 7.0).all()), k
+    saved_n, scr_n, _ = _layout(lib, 40, 1, 41, 0)
+    assert torch.isnan(out["saved"][saved_n:]).all() and torch.isnan(out["scratch"][scr_n:]).all()
+    y[7] = -1
+    assert torch.isnan(_classifier(lib, x, H, W, b, y)["loss"][0])
+    assert lib.cpc_device_error_flags(1) == LABEL_RANGE
+    xc, Wc, bc, labels = _ctc_inputs(13, Bq=2, S=16)
+    labels[1, 3] = 41                                     # the blank is not a target
+    loss, dl, out, saved = _ctc(lib, xc, Wc, bc, labels, canary=canary)
+    assert torch.isnan(loss[0]) and bool((loss[1:] == 7.0).all()) and bool((dl[2 * 16 * 42:] == 7.0).all())
+    assert torch.isnan(saved[_layout(lib, 2, 16, 42, 1)[0]:]).all()
+    assert lib.cpc_device_error_flags(1) == LABEL_RANGE
+
+
+def test_shapes_are_checked_before_any_launch_emulated():
+    lib = emu()
+    sizes = (ctypes.c_long * 3)()
+    assert lib.cpc_supervised_layout(4, 513, 42, 1, sizes) == 1          # CPC_ERR_SHAPE: CTC beyond 512 frames
+    assert lib.cpc_supervised_layout(4, 512, 42, 1, sizes) == 0
+    assert lib.cpc_supervised_layout(4, 513, 42, 0, sizes) == 0          # the classifier has no such limit
+    for bad in [(0, 1, 41, 0), (4, 0, 41, 0), (4, 1, 1, 0), (4, 1, 8193, 0), (1 << 20, 1, 4096, 0)]:
+        assert lib.cpc_supervised_layout(*bad, sizes) == 1, bad
+    assert lib.cpc_supervised_layout(4, 1, 41, 2, sizes) == 2 and lib.cpc_supervised_layout(4, 1, 41, 0, None) == 2
+    x = torch.full((4 * 513 * H,), 7.0)
+    W, b = torch.zeros(42, H), torch.zeros(42)
+    labels = torch.zeros(4, 513, dtype=torch.long)
+    saved, loss = torch.full((64,), 7.0), torch.full((1,), 7.0)
+    assert lib.cpc_ctc_forward(P(x), P(W), P(b), P(labels), P(saved), P(loss), 4, 513, 42, None) == 1
+    assert lib.cpc_ctc_backward(P(saved), P(loss), P(saved), 4, 513, 42, None) == 1
+    acc = torch.zeros(1, dtype=torch.float64)
+    assert lib.cpc_classifier_forward(P(x), 255, P(W), P(b), P(labels), P(saved), P(loss), P(acc), 4, 42, None) == 2
+    assert lib.cpc_classifier_forward(P(x), H, P(W), P(b), None, P(saved), P(loss), P(acc), 4, 42, None) == 2
+    assert lib.cpc_classifier_backward(P(x), H, P(W), None, None, None, None, P(saved), P(saved), P(saved), None, 4, 42,
+                                       None) == 2                       # neither dlogits nor what makes them
+    assert bool((saved == 7.0).all()) and bool((loss == 7.0).all())
+
+
+def test_identical_calls_give_identical_bits_emulated():
+    lib = emu()
+    x, W, b, y = _case(700, 300, seed=21)                 # three row slabs for dW / db
+    a1, a2 = _classifier(lib, x, H, W, b, y), _classifier(lib, x, H, W, b, y)
+    for k in ("loss", "acc", "dW", "db", "dX"):
+        assert torch.equal(a1[k], a2[k]), k
+    xc, Wc, bc, labels = _ctc_inputs(14, Bq=2, S=40)
+    c1, c2 = _ctc(lib, xc, Wc, bc, labels), _ctc(lib, xc, Wc, bc, labels)
+    assert torch.equal(c1[0], c2[0]) and torch.equal(c1[1], c2[1])
+    for k in ("dW", "db", "dX"):
+        assert torch.equal(c1[2][k], c2[2][k]), k

@@ -1,0 +1,250 @@
+"""Supervised criteria on the MI355X (csrc/supervised.hip through ops.ClassifierXentFunction / ops.CtcXentFunction): parity with
+torch in float64, the reference's fixture, no host synchronisation, and linear-separability training through harness.train_epoch
+against the reference's torch formulation."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import supervised_util as U
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden")
+
+
+def _dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    return torch.device("cuda:0")
+
+
+def _rel(a, b):
+    return ((a.double() - b.double()).norm() / (b.double().norm() + 1e-30)).item()
+
+
+def _xent64(x, W, b, y):
+    xr, Wr, br = (t.double().detach().clone().requires_grad_(True) for t in (x, W, b))
+    logits = F.linear(xr, Wr, br)
+    loss = F.cross_entropy(logits, y)
+    loss.backward()
+    return loss.detach(), logits.detach(), Wr.grad, br.grad, xr.grad
+
+
+def _acc_ok(acc, logits, y):
+    top2 = logits.topk(2, dim=1).values
+    close = (top2[:, 0] - top2[:, 1]) < 1e-5 * logits.abs().max(dim=1).values.clamp_min(1e-30)
+    hit = logits.argmax(dim=1) == y
+    lo, hi = (hit & ~close).double().mean().item(), (hit | close).double().mean().item()
+    return lo - 1e-15 <= acc <= hi + 1e-15
+
+
+@pytest.mark.parametrize("B,kind,C", [(B, k, C) for B in (8, 64) for k, C in (("phone", 41), ("speaker", 12), ("phone", 300))]
+                         + [(64, "speaker", 8192)])
+def test_classifier_parity_float64(B, kind, C):
+    dev = _dev()
+    from cpc_audio_amd.ops import ClassifierXentFunction
+    g = torch.Generator().manual_seed(B + C)
+    S = 128
+    c = torch.randn(B, S, 256, generator=g).to(dev).requires_grad_(True)
+    W = (0.1 * torch.randn(C, 256, generator=g)).to(dev).requires_grad_(True)
+    b = (0.1 * torch.randn(C, generator=g)).to(dev).requires_grad_(True)
+    if kind == "speaker":
+        x, y = c[:, -1, :], torch.randint(0, C, (B,), generator=g).to(dev)
+    else:
+        x, y = c.view(B * S, 256), torch.randint(0, C, (B * S,), generator=g).to(dev)
+    loss, acc = ClassifierXentFunction.apply(x, y, W, b)
+    assert loss.shape == acc.shape == (1, 1) and acc.dtype == torch.float64 and not acc.requires_grad
+    loss.backward()
+    rl, logits, rdW, rdb, rdx = _xent64(x, W, b, y)
+    assert abs(loss.item() - rl.item()) <= 1e-5 * abs(rl.item())
+    assert _acc_ok(acc.item(), logits, y)
+    assert _rel(W.grad, rdW) < 1e-5 and _rel(b.grad, rdb) < 1e-5
+    dc = c.grad.view(B, S, 256)
+    if kind == "speaker":
+        assert _rel(dc[:, -1], rdx) < 1e-5 and bool((dc[:, :-1] == 0).all())
+    else:
+        assert _rel(dc.view(B * S, 256), rdx) < 1e-5
+
+
+def _ctc64(c, W, b, labels):
+    cr, Wr, br = (t.double().detach().clone().requires_grad_(True) for t in (c, W, b))
+    B, S, _ = c.shape
+    lp = F.log_softmax(F.linear(cr, Wr, br), dim=2).permute(1, 0, 2)
+    keep = torch.ones_like(labels, dtype=torch.bool)
+    keep[:, 1:] = labels[:, 1:] != labels[:, :-1]
+    loss = F.ctc_loss(lp, labels[keep], torch.full((B,), S, dtype=torch.long, device=c.device), keep.sum(1),
+                      blank=W.shape[0] - 1, zero_infinity=True)
+    loss.backward()
+    return loss.detach(), Wr.grad, br.grad, cr.grad
+
+
+@pytest.mark.parametrize("B", [8, 64])
+def test_ctc_parity_float64(B):
+    dev = _dev()
+    from cpc_audio_amd.ops import CtcXentFunction
+    g = torch.Generator().manual_seed(B)
+    S = 128
+    c = torch.randn(B, S, 256, generator=g).to(dev).requires_grad_(True)
+    W = (0.1 * torch.randn(42, 256, generator=g)).to(dev).requires_grad_(True)
+    b = (0.1 * torch.randn(42, generator=g)).to(dev).requires_grad_(True)
+    labels = U.frame_labels(41, B, S, seed=B).to(dev)
+    loss = CtcXentFunction.apply(c, labels, W, b)
+    loss.backward()
+    rl, rdW, rdb, rdc = _ctc64(c, W, b, labels)
+    assert abs(loss.item() - rl.item()) <= 1e-5 * abs(rl.item())
+    assert _rel(W.grad, rdW) < 1e-4 and _rel(b.grad, rdb) < 1e-4 and _rel(c.grad, rdc) < 1e-4
+    with pytest.raises(ValueError, match="512"):
+        CtcXentFunction.apply(torch.zeros(1, 513, 256, device=dev), torch.zeros(1, 513, dtype=torch.long, device=dev), W, b)
+
+
+@pytest.mark.parametrize("name", ["speaker", "phone", "phone_enc", "ctc"])
+def test_modules_match_the_reference_fixture(name):
+    dev = _dev()
+    from cpc_audio_amd import criterion as CR
+    meta = json.load(open(os.path.join(GOLD, "supervised_meta.json")))["cases"][name]
+    data = np.load(os.path.join(GOLD, "supervised.npz"))
+    cls, args, dim = U.CASES[name]
+    crit = getattr(CR, cls)(*args)
+    assert crit.hip_path
+    shapes = {k: tuple(v) for k, v in meta["keys"].items()}
+    crit.load_state_dict(U.seeded_state(shapes, meta["param_seed"]), strict=True)
+    crit.to(dev)
+    c, enc = U.features(dim, meta["input_seed"])
+    loss, acc, grads, dc, de = U.run(crit, name, c.to(dev), enc.to(dev), torch.from_numpy(data["phone_labels"]).to(dev),
+                                     torch.from_numpy(data["speaker_labels"]).to(dev))
+    ref = float(data[f"{name}:loss"].reshape(-1)[0])
+    assert loss.shape == (1, 1) and loss.dtype == torch.float32 and abs(loss.item() - ref) <= 1e-5 * abs(ref)
+    assert acc.shape == (1, 1) and acc.dtype == (torch.float32 if name == "ctc" else torch.float64)
+    assert acc.item() == float(data[f"{name}:acc"].reshape(-1)[0])
+    tol = 1e-4 if name == "ctc" else 1e-5
+    for k, gr in grads.items():
+        r = torch.from_numpy(data[f"{name}:grad:{k}"])
+        if name not in U.FULL_GRADS and gr.dim() == 2 and gr.shape[1] >= 128:
+            gr = gr.cpu() @ U.projection(gr.shape[1])
+        assert _rel(gr.cpu(), r) < tol, k
+    P = U.projection(dim)
+    for t, key in ((dc, "dc"), (de, "de")):
+        if f"{name}:{key}" in data:
+            r = torch.from_numpy(data[f"{name}:{key}"])
+            assert _rel(t.cpu() @ P, r) < tol, key
+            assert abs(t.norm().item() - meta[f"{key}_norm"]) <= tol * meta[f"{key}_norm"]
+        else:
+            assert t is None
+
+
+def test_forward_backward_without_host_synchronisation():
+    dev = _dev()
+    from cpc_audio_amd.criterion import CTCPhoneCriterion, PhoneCriterion, SpeakerCriterion
+    crits = [SpeakerCriterion(256, 12).to(dev), PhoneCriterion(256, 41, False).to(dev), CTCPhoneCriterion(256, 41, False).to(dev)]
+    c = torch.randn(8, 128, 256, device=dev, requires_grad=True)
+    spk = torch.randint(0, 12, (8,), device=dev)
+    ph = U.frame_labels(41, 8, 128).to(dev)
+    for crit in crits:                                            # warm: layouts cached, library bound
+        crit(c, c, spk if isinstance(crit, SpeakerCriterion) else ph)[0].sum().backward()
+    torch.cuda.synchronize()
+    try:
+        torch.cuda.set_sync_debug_mode("error")
+        try:
+            torch.zeros(1, device=dev).item()
+            honoured = False
+        except RuntimeError:
+            honoured = True
+        if honoured:
+            for crit in crits:
+                loss, acc = crit(c, c, spk if isinstance(crit, SpeakerCriterion) else ph)
+                torch.autograd.backward([loss], [torch.ones_like(loss)])
+    finally:
+        torch.cuda.set_sync_debug_mode(0)
+    if not honoured:
+        pytest.skip("this ROCm build of torch does not honour torch.cuda.set_sync_debug_mode('error')")
+    torch.cuda.synchronize()
+    assert torch.isfinite(c.grad).all()
+
+
+class _PhoneLoader:
+    def __init__(self, n, B, seed, dev):
+        g = torch.Generator().manual_seed(seed)
+        self.items = [((0.1 * torch.randn(B, 1, 20480, generator=g)).clamp_(-1, 1).to(dev),
+                       U.frame_labels(41, B, 128, seed=seed + i).to(dev)) for i in range(n)]
+
+    def __iter__(self):
+        return iter(self.items)
+
+    def __len__(self):
+        return len(self.items)
+
+
+def test_frozen_linear_separability_matches_the_torch_formulation():
+    """linear_separability.py:244-256: the CPC model frozen, Adam on the classifier only -- three harness.train_epoch steps
+    with the HIP criterion against the same three steps of nn.Linear + nn.CrossEntropyLoss on the same features."""
+    dev = _dev()
+    from cpc_audio_amd import harness as H
+    from cpc_audio_amd.criterion import PhoneCriterion
+    from cpc_audio_amd.train import build_model
+    torch.manual_seed(0)
+    model = build_model().to(dev)
+    for p in model.parameters():
+        p.requires_grad = False
+    crit = PhoneCriterion(256, 41, False).to(dev)
+    ref = torch.nn.Linear(256, 41).to(dev)
+    ref.load_state_dict({k.split(".", 1)[1]: v for k, v in crit.state_dict().items()})
+    loader = _PhoneLoader(3, 8, 11, dev)
+    opt = torch.optim.Adam(crit.parameters(), lr=2e-3)
+    logs = H.train_epoch(loader, model, crit, opt)
+    assert logs["iter"] == 3 and np.isfinite(logs["locLoss_train"]).all()
+    ropt = torch.optim.Adam(ref.parameters(), lr=2e-3)
+    model.train()
+    for wave, label in loader:
+        with torch.no_grad():
+            c, _, _ = model(wave, label)
+        loss = F.cross_entropy(ref(c.reshape(-1, 256)), label.reshape(-1))
+        ropt.zero_grad()
+        loss.backward()
+        ropt.step()
+    for k, v in crit.state_dict().items():
+        r = ref.state_dict()[k.split(".", 1)[1]]
+        assert (v - r).abs().max().item() <= 1e-5, k
+    val = H.val_epoch(loader, model, crit)
+    assert val["iter"] == 3 and np.isfinite(val["locLoss_val"]).all()
+
+
+@pytest.mark.parametrize("kind", ["phone", "ctc", "speaker"])
+def test_unfrozen_step_reaches_the_model(kind):
+    """train.py --supervised: gradients reach the GRU and the encoder through dX; dc matches the torch formulation."""
+    dev = _dev()
+    from cpc_audio_amd import harness as H
+    from cpc_audio_amd.criterion import CTCPhoneCriterion, PhoneCriterion, SpeakerCriterion
+    from cpc_audio_amd.train import build_model
+    torch.manual_seed(1)
+    model = build_model().to(dev)
+    crit = {"phone": lambda: PhoneCriterion(256, 41, False), "ctc": lambda: CTCPhoneCriterion(256, 41, False),
+            "speaker": lambda: SpeakerCriterion(256, 12)}[kind]().to(dev)
+    loader = _PhoneLoader(1, 8, 21, dev)
+    wave, label = loader.items[0]
+    if kind == "speaker":
+        label = label[:, 0] % 12
+        loader.items = [(wave, label)]
+    c = model(wave, label)[0].detach().requires_grad_(True)
+    loss = crit(c, c, label)[0]
+    loss.backward()
+    lin = crit.linearSpeakerClassifier if kind == "speaker" else crit.PhoneCriterionClassifier
+    cr = c.detach().double().requires_grad_(True)
+    W, b = lin.weight.detach().double(), lin.bias.detach().double()
+    if kind == "phone":
+        F.cross_entropy(F.linear(cr.reshape(-1, 256), W, b), label.reshape(-1)).backward()
+    elif kind == "speaker":
+        F.cross_entropy(F.linear(cr[:, -1], W, b), label).backward()
+    else:
+        _, _, _, g = _ctc64(c.detach(), lin.weight, lin.bias, label)
+        cr.grad = g
+    assert _rel(c.grad, cr.grad) < (1e-4 if kind == "ctc" else 1e-5)
+    before = [p.detach().clone() for p in model.parameters()]
+    opt = torch.optim.Adam(list(model.parameters()) + list(crit.parameters()), lr=1e-4)
+    logs = H.train_epoch(loader, model, crit, opt)
+    assert logs["iter"] == 1 and np.isfinite(logs["locLoss_train"]).all()
+    moved = [not torch.equal(p0, p.detach()) for p0, p in zip(before, model.parameters())]
+    assert all(moved)
