@@ -1,0 +1,394 @@
+// ABX discrimination (cpc/eval/ABX.py, cpc/eval/ABX/{abx_group_computation.py,dtw.pyx} of the reference): frame distances,
+// DTW and the per-group score theta, batched over a whole evaluation pass.
+//
+// Frames live once on the device as packed (T, D) fp32 rows; a segment is (offset, length) into them.  Every DTW runs on ONE
+// wave and is a pure function of (row segment, column segment, metric), wherever its pair sits in a launch:
+//   frame distance   cosine: acos(clamp(<x, y>, -1, 1)) / pi on the (H+1)-wide normalised frames; euclidean: sqrt(sum (x - y)^2),
+//                    both a k-ordered exact-f32 fmaf chain (no split arithmetic: acos is ill-conditioned near 1)
+//   DTW              anti-diagonal sweep, one row per lane, row blocks of 64 with the block's last row handed over in LDS.
+//                    Every cell sees the same three fp32 operands as dtw.pyx's row-major loop, so the cost matrix is the same.
+//                    The backtracked path length is carried FORWARD: the move the backtrack takes at (i, j) compares exactly the
+//                    neighbours the min saw, so L(i, j) = 1 + L(move(i, j)), L(i, 0) = i + 1, L(0, j) = j + 1, and the path length
+//                    is L(N-1, M-1) -- no move bits, no second pass, no scratch for long segments.  cost / L is IEEE division.
+//   fast path        rows <= 64 and rows * cols <= kAbxCells: the wave first fills the pair's distance matrix into its LDS slice
+//                    with all 64 lanes busy, then sweeps it.  Otherwise the sweep computes each cell's distance on the fly (the
+//                    same function, so the same bits) and the LDS slice holds the row hand-over.
+// Kernels:
+//   abx_pairs_kernel   one workgroup per (group, x member), its four waves stream the group's A and B members: dxa (Nx, Na) and
+//                      dxb (Nx, Nb) of the group at pair_base[g] in the caller's scratch.  Symmetric (within) mode computes only
+//                      j > i with x_i as the rows and mirrors it, as dtw_batch does; the diagonal is written 0.
+//   abx_score_kernel   one wave per group: dxa[i, i] = max(dxb) + 1 (symmetric), integer counts of < and == over (Nx, Na, Nb),
+//                      theta = f32(cnt_lt + f32(0.5 cnt_eq)) / (n_pos Nb), score = 1 - theta.
+//   abx_pairlist_kernel / abx_dtw_kernel: the same wave DTW on a pair list / on the caller's precomputed distance tensor.
+#include "cpc_common.h"
+#include "cpc_internal.h"
+
+namespace cpc {
+
+constexpr int kAbxMaxDim = 1024;     // feature width D
+constexpr int kAbxMaxLen = 1024;     // frames per segment (the row hand-over keeps one row of costs + lengths in LDS)
+constexpr int kAbxWaves = 4;         // waves per workgroup
+constexpr int kAbxCells = 2 * kAbxMaxLen;   // floats of each wave's LDS slice: the fast path's distance matrix or the hand-over
+constexpr float kAbxPi = 3.14159265358979323846f;
+
+// Set (bit 0) when a plan named a segment outside [0, n_seg) or a segment's (offset, length) lay outside the frames; read and
+// cleared by cpc_device_error_flags() (capi.hip) as CPC_DEVERR_ABX_INDEX.  The id is clamped for addressing, the group's score NaN.
+static __device__ unsigned g_abx_index = 0;
+
+struct AbxFeat {
+    const float* feat;      // (n_frames, D)
+    const int* seg_off;     // (n_seg)
+    const int* seg_len;     // (n_seg)
+    int n_seg;
+    long n_frames;
+    int D, max_len, metric;     // metric 0 cosine, 1 euclidean
+};
+
+// Segment id -> (frame offset, length), clamped into range; returns false if anything had to be clamped.
+__device__ __forceinline__ bool abx_segment(const AbxFeat& f, int id, long& off, int& len) {
+    bool ok = id >= 0 && id < f.n_seg;
+    id = min(max(id, 0), f.n_seg - 1);
+    long o = f.seg_off[id];
+    int l = f.seg_len[id];
+    if (l < 1 || l > f.max_len || o < 0 || o + l > f.n_frames) {
+        ok = false;
+        l = min(max(l, 1), f.max_len);
+        l = (int)(l < f.n_frames ? l : f.n_frames);
+        o = o < 0 ? 0 : (o + l > f.n_frames ? f.n_frames - l : o);
+    }
+    off = o;
+    len = l;
+    return ok;
+}
+
+__device__ __forceinline__ float abx_frame_dist(const float* __restrict__ x, const float* __restrict__ y, int D, int metric) {
+    float s = 0.f;
+    if (metric == 0) {
+        for (int k = 0; k < D; ++k) s = fmaf(x[k], y[k], s);
+        s = s < -1.f ? -1.f : (s > 1.f ? 1.f : s);        // torch.clamp (NaN passes through)
+        return acosf(s) / kAbxPi;
+    }
+    for (int k = 0; k < D; ++k) {
+        const float t = x[k] - y[k];
+        s = fmaf(t, t, s);
+    }
+    return sqrtf(s);
+}
+
+struct AbxFeatDist {
+    const float* x;     // first row frame of the row segment
+    const float* y;     // first frame of the column segment
+    int D, metric;
+    __device__ float operator()(int r, int c) const { return abx_frame_dist(x + (long)r * D, y + (long)c * D, D, metric); }
+};
+
+struct AbxMatDist {
+    const float* m;     // (R, ld) block of the caller's distance tensor
+    int ld;
+    __device__ float operator()(int r, int c) const { return m[(long)r * ld + c]; }
+};
+
+// DTW of an R x C distance matrix (dtw.pyx:_dtw, normalized) on the calling wave; every lane returns the result.  `slice` is the
+// wave's own kAbxCells floats of LDS.  R, C in [1, kAbxMaxLen].  Convergent: all 64 lanes call it.
+template <bool kPrefill, class Dist>
+__device__ float abx_wave_dtw(int R, int C, const Dist& dist, float* slice) {
+    const int lane = threadIdx.x & 63;
+    const bool fast = kPrefill && R <= 64 && R * C <= kAbxCells;
+    if (fast) {
+        for (int cell = lane; cell < R * C; cell += 64) slice[cell] = dist(cell / C, cell % C);
+        __builtin_amdgcn_wave_barrier();
+    }
+    float* hand_cost = slice;                   // the previous row block's last row (slow path only)
+    float* hand_len = slice + kAbxMaxLen;
+    float left = 0.f, left_len = 0.f;           // this lane's last cell (r, c - 1); lengths as floats (exact below 2^24)
+    int last_rows = 1;
+    for (int r0 = 0; r0 < R; r0 += 64) {
+        const int rows = min(64, R - r0);
+        const int r = r0 + lane;
+        const bool hand_out = lane == 63 && r0 + 64 < R;
+        float up_prev = 0.f, up_prev_len = 0.f;  // the cell above-left: what lane - 1 held two steps ago
+        left = 0.f;
+        left_len = 0.f;
+        for (int t = 0; t < rows + C - 1; ++t) {
+            const int c = t - lane;
+            const float up_n = __shfl_up(left, 1);          // lane - 1's cell of the previous step: (r - 1, c)
+            const float up_n_len = __shfl_up(left_len, 1);
+            if (lane < rows && c >= 0 && c < C) {
+                const float d = fast ? slice[lane * C + c] : dist(r, c);
+                float up = up_n, up_len = up_n_len, dg = up_prev, dg_len = up_prev_len;
+                if (lane == 0 && r > 0) {
+                    up = hand_cost[c];
+                    up_len = hand_len[c];
+                    if (c > 0) {
+                        dg = hand_cost[c - 1];
+                        dg_len = hand_len[c - 1];
+                    }
+                }
+                float cost, len;
+                if (r == 0) {
+                    cost = c == 0 ? d : d + left;
+                    len = (float)(c + 1);
+                } else if (c == 0) {
+                    cost = d + up;
+                    len = (float)(r + 1);
+                } else {
+                    float m = up < dg ? up : dg;
+                    m = left < m ? left : m;
+                    cost = d + m;
+                    // the backtrack's rule at this cell: diag if c_diag <= c_left and c_diag <= c_up, else left if c_left <= c_up
+                    len = (dg <= left && dg <= up) ? dg_len + 1.f : (left <= up ? left_len + 1.f : up_len + 1.f);
+                }
+                left = cost;
+                left_len = len;
+                if (hand_out) {
+                    hand_cost[c] = cost;
+                    hand_len[c] = len;
+                }
+            }
+            up_prev = up_n;
+            up_prev_len = up_n_len;
+        }
+        last_rows = rows;
+    }
+    const float cost = __shfl(left, last_rows - 1);
+    const float len = __shfl(left_len, last_rows - 1);
+    __builtin_amdgcn_wave_barrier();            // the slice is free for the wave's next pair
+    return (float)((double)cost / (double)len);
+}
+
+// ------------------------------------------------------------------ group scorer
+struct AbxPlan {
+    const int* members;         // member segment ids, per group A, then B, then X
+    const int* groups;          // (G, 4): first member, Na, Nb, Nx
+    const long long* pair_base; // (G): the group's dxa then dxb in `dist`
+    const int* work;            // (W, 2): group, x member
+    int G, W, symmetric;
+    float* dist;
+    float* scores;              // (G)
+};
+
+__global__ __launch_bounds__(256) void abx_pairs_kernel(AbxFeat f, AbxPlan p) {
+    __shared__ float lds[kAbxWaves][kAbxCells];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int g = min(max(p.work[2 * blockIdx.x], 0), p.G - 1);
+    const int* gr = p.groups + 4 * g;
+    const int first = gr[0], Na = gr[1], Nb = gr[2], Nx = gr[3];
+    const int i = min(max(p.work[2 * blockIdx.x + 1], 0), Nx - 1);
+    if (Na < 1 || Nb < 1 || Nx < 1) return;     // the score kernel reports the group
+    const int* mem = p.members + first;
+    float* dxa = p.dist + p.pair_base[g];
+    float* dxb = dxa + (long)Nx * Na;
+    long xo;
+    int xl;
+    (void)abx_segment(f, mem[Na + Nb + i], xo, xl);
+    for (int j = wave; j < Na + Nb; j += kAbxWaves) {
+        const bool in_a = j < Na;
+        if (in_a && p.symmetric && j <= i) {
+            if (j == i && lane == 0) dxa[(long)i * Na + i] = 0.f;
+            continue;
+        }
+        long yo;
+        int yl;
+        (void)abx_segment(f, mem[j], yo, yl);
+        const AbxFeatDist dist{f.feat + xo * f.D, f.feat + yo * f.D, f.D, f.metric};
+        const float v = abx_wave_dtw<true>(xl, yl, dist, lds[wave]);
+        if (lane == 0) {
+            if (!in_a) {
+                dxb[(long)i * Nb + (j - Na)] = v;
+            } else {
+                dxa[(long)i * Na + j] = v;
+                if (p.symmetric) dxa[(long)j * Na + i] = v;
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ int abx_wave_isum(int v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void abx_score_kernel(AbxFeat f, AbxPlan p) {
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * kAbxWaves + (threadIdx.x >> 6);
+    if (g >= p.G) return;                                   // wave-uniform; no barrier below
+    const int* gr = p.groups + 4 * g;
+    const int first = gr[0], Na = gr[1], Nb = gr[2], Nx = gr[3];
+    bool bad = Na < 1 || Nb < 1 || Nx < 1 || (p.symmetric && Nx != Na);
+    if (!bad) {
+        for (int m = lane; m < Na + Nb + Nx; m += 64) {
+            long o;
+            int l;
+            if (!abx_segment(f, p.members[first + m], o, l)) bad = true;
+        }
+    }
+    bad = __any(bad);
+    if (bad) {
+        if (lane == 0) {
+            atomicOr(&g_abx_index, 1u);
+            p.scores[g] = __builtin_nanf("");
+        }
+        return;
+    }
+    const float* dxa = p.dist + p.pair_base[g];
+    const float* dxb = dxa + (long)Nx * Na;
+    float diag = 0.f;
+    if (p.symmetric) {
+        float m = -INFINITY;
+        for (int e = lane; e < Nx * Nb; e += 64) m = fmaxf(m, dxb[e]);
+        diag = (float)((double)wave_max(m) + 1.0);          // dxa[i, i] = dxb.max().item() + 1
+    }
+    int lt = 0, eq = 0;
+    const int ab = Na * Nb;
+    for (int e = lane; e < Nx * ab; e += 64) {
+        const int x = e / ab, rem = e - x * ab, a = rem / Nb, b = rem - a * Nb;
+        const float va = (p.symmetric && x == a) ? diag : dxa[(long)x * Na + a];
+        const float vb = dxb[(long)x * Nb + b];
+        lt += va < vb;
+        eq += va == vb;
+    }
+    lt = abx_wave_isum(lt);
+    eq = abx_wave_isum(eq);
+    if (lane == 0) {
+        const long n_pos = p.symmetric ? (long)Na * (Na - 1) : (long)Na * Nx;
+        const float sc = (float)lt + 0.5f * (float)eq;
+        const float theta = sc / (float)(n_pos * Nb);
+        p.scores[g] = 1.f - theta;
+    }
+}
+
+// ------------------------------------------------------------------ pair list / DTW only
+__global__ __launch_bounds__(256) void abx_pairlist_kernel(AbxFeat f, const int* __restrict__ pairs, int n_pairs,
+                                                          float* __restrict__ out) {
+    __shared__ float lds[kAbxWaves][kAbxCells];
+    const int wave = threadIdx.x >> 6;
+    const int q = blockIdx.x * kAbxWaves + wave;
+    if (q >= n_pairs) return;                               // wave-uniform; the DTW has no block barrier
+    long xo, yo;
+    int xl, yl;
+    const bool ok = abx_segment(f, pairs[2 * q], xo, xl) & abx_segment(f, pairs[2 * q + 1], yo, yl);
+    const AbxFeatDist dist{f.feat + xo * f.D, f.feat + yo * f.D, f.D, f.metric};
+    const float v = abx_wave_dtw<true>(xl, yl, dist, lds[wave]);
+    if ((threadIdx.x & 63) == 0) {
+        out[q] = ok ? v : __builtin_nanf("");
+        if (!ok) atomicOr(&g_abx_index, 1u);
+    }
+}
+
+struct AbxMat {
+    const float* dist;      // (N1, N2, S1, S2)
+    const int* size1;       // (N1)
+    const int* size2;       // (N2)
+    int N1, N2, S1, S2, ignore_diag, symmetric;
+    float* out;             // (N1, N2)
+};
+
+__global__ __launch_bounds__(256) void abx_dtw_kernel(AbxMat m) {
+    __shared__ float lds[kAbxWaves][kAbxCells];
+    const int wave = threadIdx.x >> 6;
+    const long q = (long)blockIdx.x * kAbxWaves + wave;
+    if (q >= (long)m.N1 * m.N2) return;
+    const int i = (int)(q / m.N2), j = (int)(q - (long)i * m.N2);
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    if ((m.symmetric && j < i) || (m.ignore_diag && i == j)) {     // dtw_batch leaves these to the mirror (or zero)
+        if (lane0 && !(m.symmetric && j < i)) m.out[q] = 0.f;
+        return;
+    }
+    int R = m.size1[i], C = m.size2[j];
+    const bool ok = R >= 1 && R <= m.S1 && C >= 1 && C <= m.S2;
+    R = min(max(R, 1), m.S1);
+    C = min(max(C, 1), m.S2);
+    const AbxMatDist dist{m.dist + q * m.S1 * m.S2, m.S2};
+    const float v = abx_wave_dtw<false>(R, C, dist, lds[wave]);
+    if (lane0) {
+        const float r = ok ? v : __builtin_nanf("");
+        m.out[q] = r;
+        if (m.symmetric && i != j) m.out[(long)j * m.N2 + i] = r;
+        if (!ok) atomicOr(&g_abx_index, 1u);
+    }
+}
+
+int abx_error_flag_fetch(int clear, unsigned* out) {
+    unsigned v = 0;
+    if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_abx_index), sizeof(v)) != hipSuccess) return CPC_ERR_ARG;
+    if (clear && v) {
+        const unsigned zero = 0;
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_abx_index), &zero, sizeof(zero)) != hipSuccess) return CPC_ERR_ARG;
+    }
+    *out = v;
+    return 0;
+}
+
+static int abx_feat(const float* feat, const int* seg_off, const int* seg_len, int n_seg, long n_frames, int D, int max_len,
+                    int metric, AbxFeat* f) {
+    CPC_RETURN_IF(!feat || !seg_off || !seg_len || (metric != 0 && metric != 1), CPC_ERR_ARG);
+    CPC_RETURN_IF(D < 1 || D > kAbxMaxDim || max_len < 1 || max_len > kAbxMaxLen || n_seg < 1 || n_frames < 1 ||
+                  n_frames > (long)INT32_MAX, CPC_ERR_SHAPE);
+    *f = AbxFeat{feat, seg_off, seg_len, n_seg, n_frames, D, max_len, metric};
+    return 0;
+}
+
+}  // namespace cpc
+
+using namespace cpc;
+
+extern "C" int cpc_abx_layout(int D, int max_len, int n_groups, long n_pairs, long* sizes) {
+    CPC_RETURN_IF(!sizes, CPC_ERR_ARG);
+    CPC_RETURN_IF(D < 1 || D > kAbxMaxDim || max_len < 1 || max_len > kAbxMaxLen || n_groups < 0 || n_pairs < 0, CPC_ERR_SHAPE);
+    sizes[0] = n_pairs;          // floats of the pair-distance scratch (dxa, dxb of every group)
+    sizes[1] = kAbxMaxLen;       // longest segment accepted
+    sizes[2] = 64;               // rows of the fast path (and rows * columns <= sizes[3])
+    sizes[3] = kAbxCells;
+    return 0;
+}
+
+extern "C" int cpc_abx_group_scores(const float* feat, const int* seg_off, const int* seg_len, int n_seg, long n_frames, int D,
+                                    int max_len, int metric, const int* members, const int* groups, const long long* pair_base,
+                                    int n_groups, const int* work, int n_work, int symmetric, float* dist, float* scores,
+                                    void* stream) {
+    AbxFeat f;
+    const int rc = abx_feat(feat, seg_off, seg_len, n_seg, n_frames, D, max_len, metric, &f);
+    if (rc) return rc;
+    CPC_RETURN_IF(!members || !groups || !pair_base || !work || !dist || !scores || (symmetric != 0 && symmetric != 1),
+                  CPC_ERR_ARG);
+    CPC_RETURN_IF(n_groups < 0 || n_work < 0, CPC_ERR_SHAPE);
+    if (n_groups == 0) return 0;
+    const AbxPlan p{members, groups, pair_base, work, n_groups, n_work, symmetric, dist, scores};
+    hipStream_t st = (hipStream_t)stream;
+    if (n_work > 0) {
+        hipLaunchKernelGGL(abx_pairs_kernel, dim3(n_work), dim3(64 * kAbxWaves), 0, st, f, p);
+        CPC_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(abx_score_kernel, dim3(cdiv(n_groups, kAbxWaves)), dim3(64 * kAbxWaves), 0, st, f, p);
+    CPC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cpc_abx_pair_dtw(const float* feat, const int* seg_off, const int* seg_len, int n_seg, long n_frames, int D,
+                                int max_len, int metric, const int* pairs, int n_pairs, float* out, void* stream) {
+    AbxFeat f;
+    const int rc = abx_feat(feat, seg_off, seg_len, n_seg, n_frames, D, max_len, metric, &f);
+    if (rc) return rc;
+    CPC_RETURN_IF(!pairs || !out, CPC_ERR_ARG);
+    CPC_RETURN_IF(n_pairs < 0, CPC_ERR_SHAPE);
+    if (n_pairs == 0) return 0;
+    hipLaunchKernelGGL(abx_pairlist_kernel, dim3(cdiv(n_pairs, kAbxWaves)), dim3(64 * kAbxWaves), 0, (hipStream_t)stream, f,
+                       pairs, n_pairs, out);
+    CPC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cpc_abx_dtw(const float* dist, const int* size1, const int* size2, int N1, int N2, int S1, int S2, int ignore_diag,
+                           int symmetric, float* out, void* stream) {
+    CPC_RETURN_IF(!dist || !size1 || !size2 || !out || (ignore_diag != 0 && ignore_diag != 1) ||
+                  (symmetric != 0 && symmetric != 1), CPC_ERR_ARG);
+    CPC_RETURN_IF(N1 < 0 || N2 < 0 || S1 < 1 || S2 < 1 || S1 > kAbxMaxLen || S2 > kAbxMaxLen || (symmetric && N1 != N2) ||
+                  (long)N1 * N2 > (long)INT32_MAX * kAbxWaves, CPC_ERR_SHAPE);
+    if ((long)N1 * N2 == 0) return 0;
+    const AbxMat m{dist, size1, size2, N1, N2, S1, S2, ignore_diag, symmetric, out};
+    hipLaunchKernelGGL(abx_dtw_kernel, dim3((unsigned)(((long)N1 * N2 + kAbxWaves - 1) / kAbxWaves)), dim3(64 * kAbxWaves), 0,
+                       (hipStream_t)stream, m);
+    CPC_LAUNCH_CHECK();
+    return 0;
+}

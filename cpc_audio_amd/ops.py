@@ -58,6 +58,8 @@ def check_device_errors(clear=True):
                     "(outputs contain NaN from that step on)")
     if mask & 16:
         what.append("a supervised criterion received a label outside its class range (it was clamped; the loss is NaN)")
+    if mask & 32:
+        what.append("an ABX plan named a segment or size out of range (it was clamped; that score is NaN)")
     if what:
         raise _lib.CpcHipError("device-side error: " + "; ".join(what))
 

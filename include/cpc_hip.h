@@ -64,6 +64,8 @@ int cpc_get_mfma_mode(void);
  *                                waiting for another one; its outputs carry NaN from that step on
  *   CPC_DEVERR_LABEL_RANGE       a supervised criterion (cpc_classifier_forward, cpc_ctc_forward) met a label outside [0, C)
  *                                (CTC: [0, C-1)); it was clamped for addressing and the loss is NaN
+ *   CPC_DEVERR_ABX_INDEX         an ABX entry point (cpc_abx_*) met a segment id outside [0, n_seg), a segment outside the frames
+ *                                or a size outside [1, S]; it was clamped for addressing and that group's score (pair's distance) is NaN
  * The reference raises Python exceptions for such things; kernels cannot, so the wrapper (ops.check_device_errors) turns
  * the mask into a RuntimeError.  The call synchronises with the device: logging points and tests, not the step path.
  * Returns the mask (>= 0) or a negative number if the flags cannot be read. */
@@ -72,6 +74,7 @@ int cpc_get_mfma_mode(void);
 #define CPC_DEVERR_CONV_EXCHANGE 4
 #define CPC_DEVERR_LSTM_POLL_TIMEOUT 8
 #define CPC_DEVERR_LABEL_RANGE 16
+#define CPC_DEVERR_ABX_INDEX 32
 int cpc_device_error_flags(int clear);
 
 /* ---------------------------------------------------------------- encoder ----
@@ -339,6 +342,33 @@ int cpc_classifier_backward(const float* x, long ldx, const float* W, const long
 int cpc_ctc_forward(const float* x, const float* W, const float* b, const long long* labels, float* saved, float* loss, int B,
                     int S, int C, void* stream);
 int cpc_ctc_backward(const float* saved, const float* dloss, float* dlogits, int B, int S, int C, void* stream);
+
+/* ---------------------------------------------------------------- ABX evaluation ----
+ * cpc/eval/ABX.py and cpc/eval/ABX/{abx_group_computation.py, dtw.pyx}: frame distances, normalised DTW and the per-group
+ * score 1 - theta of get_theta_group_dtw, batched over a whole pass (csrc/abx.hip).
+ * Frames: feat (n_frames, D) fp32, D <= 1024; segment s is rows [seg_off[s], seg_off[s] + seg_len[s]) (int32), every length in
+ *   [1, max_len], max_len <= 1024.  metric 0: cosine, acos(clamp(<x,y>, -1, 1)) / pi (frames normalised by the caller:
+ *   normalize_with_singularity); 1: euclidean, sqrt(sum (x - y)^2).  Exact-f32 fmaf chains.  A DTW is a function of its two
+ *   segments and the metric alone: the same pair gives the same bits in any group, position or launch.
+ * cpc_abx_layout(D, max_len, n_groups, n_pairs, sizes): sizes[0] = floats of the pair scratch (n_pairs = sum over groups of
+ *   Nx (Na + Nb)), sizes[1] = longest segment accepted, sizes[2] / sizes[3] = rows / cells of the LDS fast path.
+ * cpc_abx_group_scores: plan = members (A ids, B ids, X ids per group), groups (G, 4) int32 = (first member, Na, Nb, Nx),
+ *   pair_base (G) int64 = offset of the group's dxa (Nx, Na) then dxb (Nx, Nb) in dist, work (n_work, 2) int32 = (group, x index)
+ *   for every x member of every group.  symmetric (within): X is A, only j > i is computed (x_i the rows) and mirrored, the
+ *   diagonal is written 0 and replaced by max(dxb) + 1 in the count.  scores[g] = 1 - theta, theta =
+ *   f32(cnt_lt + f32(0.5 cnt_eq)) / (n_pos Nb), n_pos = Na (Na - 1) symmetric, Na Nx otherwise.
+ * cpc_abx_pair_dtw: out[q] = DTW(rows = segment pairs[2q], columns = segment pairs[2q + 1]).
+ * cpc_abx_dtw: DTW on the caller's distance tensor dist (N1, N2, S1, S2), sizes size1 (N1) / size2 (N2) int32, out (N1, N2), with
+ *   dtw_batch's ignore_diag (diagonal 0) and symmetric (j >= i computed and mirrored; N1 == N2).
+ * A segment id or size out of range is clamped for addressing, raises CPC_DEVERR_ABX_INDEX and makes that score (distance) NaN. */
+int cpc_abx_layout(int D, int max_len, int n_groups, long n_pairs, long* sizes);
+int cpc_abx_group_scores(const float* feat, const int* seg_off, const int* seg_len, int n_seg, long n_frames, int D, int max_len,
+                         int metric, const int* members, const int* groups, const long long* pair_base, int n_groups,
+                         const int* work, int n_work, int symmetric, float* dist, float* scores, void* stream);
+int cpc_abx_pair_dtw(const float* feat, const int* seg_off, const int* seg_len, int n_seg, long n_frames, int D, int max_len,
+                     int metric, const int* pairs, int n_pairs, float* out, void* stream);
+int cpc_abx_dtw(const float* dist, const int* size1, const int* size2, int N1, int N2, int S1, int S2, int ignore_diag,
+                int symmetric, float* out, void* stream);
 
 /* ---------------------------------------------------------------- transformer layer ----
  * One TransformerLayer of cpc/transformers.py:103-111 (buildTransformerAR, :130-139), d_model 256, 8 heads,
