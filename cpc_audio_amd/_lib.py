@@ -126,6 +126,10 @@ SIGNATURES = {
     "cpc_abx_group_scores": (_I, [_P, _P, _P, _I, _L, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P]),
     "cpc_abx_pair_dtw": (_I, [_P, _P, _P, _I, _L, _I, _I, _I, _P, _I, _P, _P]),
     "cpc_abx_dtw": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "cpc_ctc_decode_layout": (_I, [_I, _I, _I, _I, _P]),
+    "cpc_ctc_beam_search": (_I, [_P, _I, _L, _L, _L, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P]),
+    "cpc_nw_align_score": (_I, [_P, _L, _P, _I, _P, _L, _P, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _P,
+                                _P]),
     "cpc_nce_layout": (_I, [_I, _I, _I, _I, _P]),
     "cpc_nce_prepare": (_I, [_P] * 6 + [_I, _I, _I, _I, _P]),
     "cpc_nce_forward": (_I, [_P] * 8 + [_I, _I, _I, _I, _P]),

@@ -199,6 +199,7 @@ int enc_error_flag_fetch(int clear, unsigned* out);
 int lstm_error_flag_fetch(int clear, unsigned* out);
 int sup_error_flag_fetch(int clear, unsigned* out);
 int abx_error_flag_fetch(int clear, unsigned* out);
+int decode_error_flag_fetch(int clear, unsigned* out);
 
 static inline long align64l(long v) { return (v + 63) & ~63L; }
 

@@ -1,0 +1,508 @@
+// PER evaluation (cpc/criterion/seq_alignment.py of the reference): the CTC prefix beam search of beam_search() and the
+// Needleman-Wunsch score of NeedlemanWunschAlignScore(), batched over utterances.
+//
+// ctc_beam_kernel: one workgroup (4 waves) per sequence, the whole search in one launch.  The state between steps is the kept
+// list of at most n_keep beams, held in LEXICOGRAPHIC order of their label sequences (the reference's key order: labels ranked
+// by their decimal strings, a proper prefix first), with pb, pnb, length, last label and lcp[j] = common prefix length of beams
+// j - 1 and j.  The labels themselves live in the caller's scratch, one row of W bytes per beam, double-buffered.
+// Per step the candidates are (i, c), i a kept beam and c < P: c == blank is beam i itself, any other c the extension i + c.
+//   children   thread i walks the block of i's kept descendants (i, e_i] -- contiguous in lexicographic order -- whose next labels
+//              after s_i are non-decreasing in rank.  For every c it records a(i, c) = number of kept beams below s_i + c, or
+//              "merged" when s_i + c IS a kept beam j (then mp[j] = i: j's pnb gets i's extension term, own + ext, which is
+//              commutative, so any order of the reference's dict updates gives the same bits).  A sequence is one beam, whatever
+//              happened to its prefixes in between: deduplication is exact.
+//   key        the candidate's position in lexicographic order, as 23 bits: (a, 0, 127 - i, rank c) for an extension, (i, 1, 0, 0)
+//              for a kept beam.  Extensions that fall between the same two kept beams descend from prefixes of the lower one; the
+//              deeper parent (larger i) sorts first, then rank c; the kept beam closes its gap.
+//   select     radix select, 8 bits per pass, on (order-preserving bits of the score, key): the score's bytes first, the key's three
+//              bytes resolve the ties at the threshold.  Scores are recomputed from the kept state in every pass (a few flops), so
+//              no candidate array exists and the LDS footprint is independent of T.  A pass stops as soon as its bin holds exactly
+//              the candidates still needed; the ordinary case (distinct scores) stops after the first bytes, the all-zero case
+//              (float32 underflow) runs into the key bytes.
+//   rebuild    the selected beams are placed in key order (counting ranks), their rows copied, and the new lcp derived from the
+//              old one (range minimum) plus at most one label read.
+// After the last step the kept list is written out ranked by (score, key) descending, as the reference's final sort.
+// Arithmetic is the input dtype's, one rounding per operation, in the reference's order: pb = (pnb' + pb') p[blank],
+// pnb = pnb' p[last] (+ ext), ext = pb' p[c] when c repeats the last label, else (pb' + pnb') p[c].
+//
+// nw_score_kernel: one wave per pair; the max-plus DP of NeedlemanWunschAlignScore in float64 swept by anti-diagonals, one row
+// per lane, row blocks of 64 with the block's last row handed over in LDS (<= kNwMaxLen + 1 doubles).
+#include "cpc_common.h"
+#include "cpc_internal.h"
+
+namespace cpc {
+
+constexpr int kDecMaxKeep = 128;     // n_keep
+constexpr int kDecMaxP = 128;        // classes (blank included)
+constexpr int kDecThreads = 256;
+constexpr unsigned char kDecMerged = 255;
+constexpr int kNwMaxLen = 4096;      // hypothesis length (the hand-over row)
+
+// Set (bit 0) when a sequence length lay outside [1, T_max], blank outside [0, P) or an alignment length outside its row; read
+// and cleared by cpc_device_error_flags() (capi.hip) as CPC_DEVERR_DECODE_RANGE.  That sequence's score is NaN.
+static __device__ unsigned g_decode_range = 0;
+
+template <class T> struct DecBits;
+template <> struct DecBits<float> {
+    static constexpr int kBytes = 4;
+    static __device__ unsigned long long ord(float x) {
+        unsigned u = __float_as_uint(x);
+        if (u == 0x80000000u) u = 0;                                   // -0 == +0, as Python compares them
+        return (u & 0x80000000u) ? (unsigned long long)(~u) : (unsigned long long)(u | 0x80000000u);
+    }
+};
+template <> struct DecBits<double> {
+    static constexpr int kBytes = 8;
+    static __device__ unsigned long long ord(double x) {
+        unsigned long long u = __builtin_bit_cast(unsigned long long, x);
+        if (u == 0x8000000000000000ull) u = 0;
+        return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+    }
+};
+
+// decimal-string order of two labels (0 < 1 < 10 < 11 < ... < 19 < 2 < 20 ...; a proper prefix first)
+__device__ __forceinline__ bool dec_less(int a, int b) {
+    char da[4], db[4];
+    int na = 0, nb = 0;
+    for (int v = a; ; v /= 10) { da[na++] = (char)(v % 10); if (v < 10) break; }
+    for (int v = b; ; v /= 10) { db[nb++] = (char)(v % 10); if (v < 10) break; }
+    for (int k = 0; k < na && k < nb; ++k)
+        if (da[na - 1 - k] != db[nb - 1 - k]) return da[na - 1 - k] < db[nb - 1 - k];
+    return na < nb;
+}
+
+template <class T> struct DecState {
+    T prow[kDecMaxP];
+    T pb[2][kDecMaxKeep], pnb[2][kDecMaxKeep];
+    int len[2][kDecMaxKeep], last[2][kDecMaxKeep], lcp[2][kDecMaxKeep];
+    int mp[2][kDecMaxKeep];                               // kept parent whose extension merges into beam j, or -1
+    unsigned char a[kDecMaxKeep][kDecMaxP];               // a(i, c) or kDecMerged
+    unsigned char rank[kDecMaxP], lor[kDecMaxP];          // decimal rank of a label, label of a rank
+    int hist[256];
+    int wsum[kDecThreads / 64];
+    int sel_q[kDecMaxKeep], srt_q[kDecMaxKeep];
+    unsigned long long sel_s[kDecMaxKeep], srt_s[kDecMaxKeep];
+    unsigned sel_k[kDecMaxKeep], srt_k[kDecMaxKeep];
+    int n_sel, pick_bin, pick_need, pick_done;
+};
+
+struct DecArgs {
+    const void* probs;
+    long sb, st, sp;             // element strides of (B, T, P)
+    const int* lengths;
+    int B, T_max, P, blank, n_keep, n_out;
+    long row_w;                  // bytes of one scratch row
+    unsigned char* rows;         // (B, 2, n_keep, row_w)
+    int* labels;                 // (B, n_out, T_max)
+    int* label_len;              // (B, n_out)
+    void* scores;                // (B, n_out)
+    int* n_beams;                // (B)
+};
+
+template <class T> struct DecCand {
+    bool valid;
+    T pb, pnb;
+    unsigned long long s;
+    unsigned k;
+};
+
+template <class T>
+__device__ __forceinline__ T dec_ext(const DecState<T>& S, int cb, int i, int c) {
+    const T p = S.prow[c];
+    return (S.len[cb][i] > 0 && S.last[cb][i] == c) ? S.pb[cb][i] * p : (S.pb[cb][i] + S.pnb[cb][i]) * p;
+}
+
+template <class T>
+__device__ __forceinline__ DecCand<T> dec_eval(const DecState<T>& S, int cb, int P, int blank, int q) {
+    DecCand<T> r;
+    const int i = q / P, c = q - i * P;
+    if (c == blank) {
+        T pnb = S.len[cb][i] > 0 ? S.pnb[cb][i] * S.prow[S.last[cb][i]] : (T)0;
+        const int par = S.mp[cb][i];
+        if (par >= 0) pnb = pnb + dec_ext(S, cb, par, S.last[cb][i]);
+        r.pb = (S.pnb[cb][i] + S.pb[cb][i]) * S.prow[blank];
+        r.pnb = pnb;
+        r.valid = true;
+        r.k = ((unsigned)i << 15) | (1u << 14);
+    } else {
+        const unsigned char a = S.a[i][c];
+        r.valid = a != kDecMerged;
+        r.pb = (T)0;
+        r.pnb = dec_ext(S, cb, i, c);
+        r.k = ((unsigned)a << 15) | ((unsigned)(127 - i) << 7) | S.rank[c];
+    }
+    r.s = DecBits<T>::ord(r.pb + r.pnb);
+    return r;
+}
+
+// digit d of (s, k): the score's kBytes bytes from the top, then the key's three bytes
+template <class T>
+__device__ __forceinline__ unsigned dec_digit(unsigned long long s, unsigned k, int d) {
+    constexpr int NS = DecBits<T>::kBytes;
+    return d < NS ? (unsigned)(s >> (8 * (NS - 1 - d))) & 255u : (k >> (8 * (2 - (d - NS)))) & 255u;
+}
+
+__device__ __forceinline__ bool dec_ge(unsigned long long s, unsigned k, unsigned long long ts, unsigned tk) {
+    return s > ts || (s == ts && k >= tk);
+}
+
+template <class T>
+__global__ __launch_bounds__(kDecThreads) void ctc_beam_kernel(DecArgs g) {
+    __shared__ DecState<T> S;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, P = g.P, blank = g.blank, K = g.n_keep;
+    const int Tb = g.lengths[b];
+    T* scores = reinterpret_cast<T*>(g.scores) + (long)b * g.n_out;
+    int* lab_out = g.labels + (long)b * g.n_out * g.T_max;
+    if (Tb < 1 || Tb > g.T_max || blank < 0 || blank >= P) {
+        for (int e = tid; e < g.n_out * g.T_max; e += kDecThreads) lab_out[e] = -1;
+        if (tid < g.n_out) {
+            scores[tid] = (T)__builtin_nan("");
+            g.label_len[(long)b * g.n_out + tid] = 0;
+        }
+        if (tid == 0) {
+            g.n_beams[b] = 0;
+            atomicOr(&g_decode_range, 1u);
+        }
+        return;
+    }
+    const T* probs = reinterpret_cast<const T*>(g.probs) + (long)b * g.sb;
+    unsigned char* rows = g.rows + (long)b * 2 * K * g.row_w;
+    if (tid < P) {
+        int r = 0;
+        for (int c = 0; c < P; ++c) r += dec_less(c, tid);
+        S.rank[tid] = (unsigned char)r;
+        S.lor[r] = (unsigned char)tid;
+    }
+    if (tid < kDecMaxKeep) S.mp[0][tid] = -1;
+    if (tid == 0) {
+        S.pb[0][0] = (T)1;
+        S.pnb[0][0] = (T)0;
+        S.len[0][0] = 0;
+        S.last[0][0] = 0;
+        S.lcp[0][0] = 0;
+    }
+    __syncthreads();
+    int Kc = 1, cb = 0;
+    for (int t = 0; t < Tb; ++t) {
+        const unsigned char* orow = rows + (long)cb * K * g.row_w;
+        unsigned char* nrow = rows + (long)(1 - cb) * K * g.row_w;
+        if (tid < P) S.prow[tid] = probs[(long)t * g.st + (long)tid * g.sp];
+        // ---- children: a(i, c), merges
+        if (tid < Kc) {
+            const int i = tid, li = S.len[cb][i];
+            int e = i;
+            while (e + 1 < Kc && S.lcp[cb][e + 1] >= li) ++e;
+            int j = i + 1;
+            int nl = j <= e ? orow[(long)j * g.row_w + li] : 0;
+            for (int r = 0; r < P; ++r) {
+                const int c = S.lor[r];
+                if (c == blank) continue;
+                while (j <= e && S.rank[nl] < r) {
+                    ++j;
+                    if (j <= e) nl = orow[(long)j * g.row_w + li];
+                }
+                if (j <= e && nl == c && S.len[cb][j] == li + 1) {
+                    S.a[i][c] = kDecMerged;
+                    S.mp[cb][j] = i;
+                } else {
+                    S.a[i][c] = (unsigned char)j;
+                }
+            }
+        }
+        if (tid == 0) S.n_sel = 0;
+        __syncthreads();
+        const int Nc = Kc * P;
+        int n_merged = 0;
+        for (int j = 0; j < Kc; ++j) n_merged += S.mp[cb][j] >= 0;
+        const int n_valid = Nc - n_merged;
+        unsigned long long ts = 0;                 // the threshold: select every candidate with (s, k) >= (ts, tk)
+        unsigned tk = 0;
+        const int m = n_valid < K ? n_valid : K;
+        if (n_valid > K) {
+            constexpr int ND = DecBits<T>::kBytes + 3;
+            unsigned long long ms = 0;
+            unsigned mk = 0;
+            int need = K;
+            for (int d = 0; d < ND; ++d) {
+                S.hist[tid] = 0;
+                __syncthreads();
+                for (int base = 0; base < Nc; base += kDecThreads) {
+                    const int q = base + tid;
+                    int bin = -1;
+                    if (q < Nc) {
+                        const DecCand<T> x = dec_eval(S, cb, P, blank, q);
+                        if (x.valid && (x.s & ms) == ts && (x.k & mk) == tk) bin = (int)dec_digit<T>(x.s, x.k, d);
+                    }
+                    const int b0 = __shfl(bin, 0);
+                    if (__all(bin == b0)) {
+                        if (lane == 0 && b0 >= 0) atomicAdd(&S.hist[b0], 64);
+                    } else if (bin >= 0) {
+                        atomicAdd(&S.hist[bin], 1);
+                    }
+                }
+                __syncthreads();
+                // inclusive suffix sums over the bins (thread tid holds bin 255 - tid)
+                const int h = S.hist[255 - tid];
+                int incl = h;
+                for (int off = 1; off < 64; off <<= 1) {
+                    const int v = __shfl_up(incl, off);
+                    if (lane >= off) incl += v;
+                }
+                if (lane == 63) S.wsum[wave] = incl;
+                __syncthreads();
+                for (int w = 0; w < wave; ++w) incl += S.wsum[w];
+                if (incl >= need && incl - h < need) {
+                    S.pick_bin = 255 - tid;
+                    S.pick_need = need - (incl - h);
+                    S.pick_done = h == need - (incl - h);
+                }
+                __syncthreads();
+                const unsigned bin = (unsigned)S.pick_bin;
+                need = S.pick_need;
+                constexpr int NS = DecBits<T>::kBytes;
+                if (d < NS) {
+                    ts |= (unsigned long long)bin << (8 * (NS - 1 - d));
+                    ms |= 255ull << (8 * (NS - 1 - d));
+                } else {
+                    tk |= bin << (8 * (2 - (d - NS)));
+                    mk |= 255u << (8 * (2 - (d - NS)));
+                }
+                const bool done = S.pick_done;
+                __syncthreads();                   // everyone has read pick_* before the next pass writes them
+                if (done) break;
+            }
+        }
+        // ---- collect the selected candidates
+        for (int q = tid; q < Nc; q += kDecThreads) {
+            const DecCand<T> x = dec_eval(S, cb, P, blank, q);
+            if (x.valid && dec_ge(x.s, x.k, ts, tk)) {
+                const int slot = atomicAdd(&S.n_sel, 1);
+                S.sel_q[slot] = q;
+                S.sel_s[slot] = x.s;
+                S.sel_k[slot] = x.k;
+            }
+        }
+        __syncthreads();
+        // ---- key order
+        if (tid < m) {
+            const unsigned k = S.sel_k[tid];
+            int pos = 0;
+            for (int u = 0; u < m; ++u) pos += S.sel_k[u] < k;
+            S.srt_q[pos] = S.sel_q[tid];
+            S.srt_s[pos] = S.sel_s[tid];
+            S.srt_k[pos] = k;
+        }
+        __syncthreads();
+        // ---- rebuild the kept list in the other buffer
+        const int nb = 1 - cb;
+        if (tid < m) {
+            const int q = S.srt_q[tid], i = q / P, c = q - i * P;
+            const DecCand<T> x = dec_eval(S, cb, P, blank, q);
+            const int li = S.len[cb][i];
+            S.pb[nb][tid] = x.pb;
+            S.pnb[nb][tid] = x.pnb;
+            S.len[nb][tid] = li + (c != blank);
+            S.last[nb][tid] = c != blank ? c : S.last[cb][i];
+            int L = 0;
+            if (tid > 0) {
+                const int q1 = S.srt_q[tid - 1], i1 = q1 / P, c1 = q1 - i1 * P;
+                if (i1 == i) {
+                    L = li;
+                } else {
+                    const int lo = i1 < i ? i1 : i, hi = i1 < i ? i : i1;
+                    L = S.lcp[cb][lo + 1];
+                    for (int k = lo + 2; k <= hi; ++k) L = min(L, S.lcp[cb][k]);
+                    const int l1 = S.len[cb][i1];
+                    if (L == l1 && c1 != blank) L += orow[(long)i * g.row_w + l1] == c1;
+                    else if (L == li && c != blank) L += orow[(long)i1 * g.row_w + li] == c;
+                }
+            }
+            S.lcp[nb][tid] = L;
+        }
+        for (int u = wave; u < m; u += kDecThreads / 64) {
+            const int q = S.srt_q[u], i = q / P, c = q - i * P;
+            const int li = S.len[cb][i], nl = li + (c != blank);
+            const unsigned* src = reinterpret_cast<const unsigned*>(orow + (long)i * g.row_w);
+            unsigned* dst = reinterpret_cast<unsigned*>(nrow + (long)u * g.row_w);
+            for (int w = lane; 4 * w < nl; w += 64) {
+                unsigned v = 4 * w < li ? src[w] : 0u;
+                if (c != blank && li >= 4 * w && li < 4 * w + 4) {
+                    const int sh = 8 * (li - 4 * w);
+                    v = (v & ~(255u << sh)) | ((unsigned)c << sh);
+                }
+                dst[w] = v;
+            }
+        }
+        if (tid < kDecMaxKeep) S.mp[nb][tid] = -1;
+        __syncthreads();
+        Kc = m;
+        cb = nb;
+    }
+    // ---- output: ranked by (score, key) descending
+    const unsigned char* frow = rows + (long)cb * K * g.row_w;
+    if (tid < Kc) {                                     // srt_s / srt_k still describe the final kept list, in its order
+        int pos = 0;
+        for (int w = 0; w < Kc; ++w) pos += w != tid && dec_ge(S.srt_s[w], S.srt_k[w], S.srt_s[tid], S.srt_k[tid]);
+        S.sel_q[pos] = tid;
+    }
+    __syncthreads();
+    for (int u = wave; u < g.n_out; u += kDecThreads / 64) {
+        const int src = u < Kc ? S.sel_q[u] : -1;
+        int* out = lab_out + (long)u * g.T_max;
+        const int n = src >= 0 ? S.len[cb][src] : 0;
+        for (int e = lane; e < g.T_max; e += 64) out[e] = e < n ? (int)frow[(long)src * g.row_w + e] : -1;
+        if (lane == 0) {
+            g.label_len[(long)b * g.n_out + u] = n;
+            scores[u] = src >= 0 ? S.pb[cb][src] + S.pnb[cb][src] : (T)0;
+        }
+    }
+    if (tid == 0) g.n_beams[b] = Kc;
+}
+
+// ------------------------------------------------------------------ Needleman-Wunsch
+struct NwArgs {
+    const int* ref;
+    long ref_stride;
+    const int* ref_len;
+    int L1;
+    const int* hyp;
+    long hyp_stride;
+    const int* hyp_len;
+    int L2, B;
+    double d, m, r;
+    int normalize;
+    double* out;
+};
+
+// 64-bit values through two 32-bit shuffles
+__device__ __forceinline__ double shfl_up_f64(double v) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = __shfl_up((unsigned)u, 1), hi = __shfl_up((unsigned)(u >> 32), 1);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ double shfl_f64(double v, int src) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = __shfl((unsigned)u, src), hi = __shfl((unsigned)(u >> 32), src);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+__global__ __launch_bounds__(64) void nw_score_kernel(NwArgs g) {
+    __shared__ double hand[kNwMaxLen + 1];
+    const int lane = threadIdx.x & 63, b = blockIdx.x;
+    const int N1 = g.ref_len[b], N2 = g.hyp_len[b];
+    if (N1 < 0 || N1 > g.L1 || N2 < 0 || N2 > g.L2) {
+        if (lane == 0) {
+            g.out[b] = __builtin_nan("");
+            atomicOr(&g_decode_range, 1u);
+        }
+        return;
+    }
+    const int* ref = g.ref + (long)b * g.ref_stride;
+    const int* hyp = g.hyp + (long)b * g.hyp_stride;
+    const double d = g.d;
+    double res;
+    if (N1 == 0 || N2 == 0) {
+        res = N1 == 0 ? (double)N2 * d : (double)N1 * d;
+    } else {
+        for (int j = lane; j <= N2; j += 64) hand[j] = (double)j * d;
+        __builtin_amdgcn_wave_barrier();
+        double left = 0.0;
+        int last_rows = 1;
+        for (int r0 = 0; r0 < N1; r0 += 64) {
+            const int rows = min(64, N1 - r0);
+            const int r = r0 + lane + 1;                      // this lane's row of the DP table
+            const bool hand_out = lane == 63 && r0 + 64 < N1;
+            const int lab = lane < rows ? ref[r - 1] : 0;
+            left = (double)r * d;                             // tmp[r][0]
+            double up_prev = 0.0;                             // the cell above-left: what lane - 1 held two steps ago
+            for (int s = 0; s < rows + N2 - 1; ++s) {
+                const int j = s - lane + 1;
+                const double up_n = shfl_up_f64(left);
+                if (lane < rows && j >= 1 && j <= N2) {
+                    double up = up_n, dg = up_prev;
+                    if (lane == 0) {
+                        up = hand[j];
+                        dg = j == 1 ? (double)r0 * d : hand[j - 1];
+                    }
+                    const double match = lab == hyp[j - 1] ? g.r : g.m;
+                    const double v1 = dg + match, v2 = left + d, v3 = up + d;
+                    const double w = v3 > v2 ? v3 : v2;           // Python max(v2, v3)
+                    const double cell = w > v1 ? w : v1;          // max(v1, .)
+                    left = cell;
+                    if (hand_out) hand[j] = cell;
+                }
+                up_prev = up_n;
+            }
+            __builtin_amdgcn_wave_barrier();
+            last_rows = rows;
+        }
+        res = shfl_f64(left, last_rows - 1);
+    }
+    if (lane == 0) {
+        res = -res;
+        if (g.normalize) res = N1 == 0 ? __builtin_nan("") : res / (double)N1;
+        g.out[b] = res;
+    }
+}
+
+int decode_error_flag_fetch(int clear, unsigned* out) {
+    unsigned v = 0;
+    if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_decode_range), sizeof(v)) != hipSuccess) return CPC_ERR_ARG;
+    if (clear && v) {
+        const unsigned zero = 0;
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_decode_range), &zero, sizeof(zero)) != hipSuccess) return CPC_ERR_ARG;
+    }
+    *out = v;
+    return 0;
+}
+
+static long dec_row_width(int T_max) { return ((long)T_max + 16) / 16 * 16; }
+
+}  // namespace cpc
+
+using namespace cpc;
+
+extern "C" int cpc_ctc_decode_layout(int B, int T_max, int P, int n_keep, long* sizes) {
+    CPC_RETURN_IF(!sizes, CPC_ERR_ARG);
+    CPC_RETURN_IF(B < 0 || T_max < 1 || T_max > (1 << 24) || P < 2 || P > kDecMaxP || n_keep < 1 || n_keep > kDecMaxKeep,
+                  CPC_ERR_SHAPE);
+    sizes[0] = (long)B * 2 * n_keep * dec_row_width(T_max);   // bytes of scratch
+    sizes[1] = dec_row_width(T_max);                          // bytes of one beam's row
+    sizes[2] = (long)sizeof(DecState<double>);                // LDS bytes of the float64 search (float32: sizes[3])
+    sizes[3] = (long)sizeof(DecState<float>);
+    sizes[4] = kDecMaxKeep;
+    sizes[5] = kDecMaxP;
+    sizes[6] = kNwMaxLen;
+    return 0;
+}
+
+extern "C" int cpc_ctc_beam_search(const void* probs, int dtype, long stride_b, long stride_t, long stride_p, const int* lengths,
+                                   int B, int T_max, int P, int blank, int n_keep, int n_out, void* scratch, long scratch_bytes,
+                                   int* labels, int* label_len, void* scores, int* n_beams, void* stream) {
+    CPC_RETURN_IF(!probs || !lengths || !scratch || !labels || !label_len || !scores || !n_beams || (dtype != 0 && dtype != 1),
+                  CPC_ERR_ARG);
+    CPC_RETURN_IF(B < 0 || T_max < 1 || T_max > (1 << 24) || P < 2 || P > kDecMaxP || n_keep < 1 || n_keep > kDecMaxKeep ||
+                  n_out < 1 || n_out > n_keep, CPC_ERR_SHAPE);
+    const long row_w = dec_row_width(T_max);
+    CPC_RETURN_IF(scratch_bytes < (long)B * 2 * n_keep * row_w, CPC_ERR_SHAPE);
+    if (B == 0) return 0;
+    const DecArgs a{probs, stride_b, stride_t, stride_p, lengths, B, T_max, P, blank, n_keep, n_out, row_w,
+                    (unsigned char*)scratch, labels, label_len, scores, n_beams};
+    if (dtype == 0) hipLaunchKernelGGL(ctc_beam_kernel<float>, dim3(B), dim3(kDecThreads), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(ctc_beam_kernel<double>, dim3(B), dim3(kDecThreads), 0, (hipStream_t)stream, a);
+    CPC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cpc_nw_align_score(const int* ref, long ref_stride, const int* ref_len, int L1, const int* hyp, long hyp_stride,
+                                  const int* hyp_len, int L2, int B, double d, double m, double r, int normalize, double* out,
+                                  void* stream) {
+    CPC_RETURN_IF(!ref || !ref_len || !hyp || !hyp_len || !out || (normalize != 0 && normalize != 1), CPC_ERR_ARG);
+    CPC_RETURN_IF(B < 0 || L1 < 0 || L2 < 0 || L2 > kNwMaxLen || ref_stride < L1 || hyp_stride < L2, CPC_ERR_SHAPE);
+    if (B == 0) return 0;
+    const NwArgs a{ref, ref_stride, ref_len, L1, hyp, hyp_stride, hyp_len, L2, B, d, m, r, normalize, out};
+    hipLaunchKernelGGL(nw_score_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, a);
+    CPC_LAUNCH_CHECK();
+    return 0;
+}

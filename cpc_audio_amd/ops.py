@@ -60,6 +60,8 @@ def check_device_errors(clear=True):
         what.append("a supervised criterion received a label outside its class range (it was clamped; the loss is NaN)")
     if mask & 32:
         what.append("an ABX plan named a segment or size out of range (it was clamped; that score is NaN)")
+    if mask & 64:
+        what.append("a PER decode or alignment received a length outside its row or a blank outside [0, P) (that score is NaN)")
     if what:
         raise _lib.CpcHipError("device-side error: " + "; ".join(what))
 
@@ -1021,3 +1023,16 @@ class TransformerLayerFunction(torch.autograd.Function):
                       "transformer_layer_backward")
         _wait(ctx.step, final=False)
         return (dx, None, None, *grads)
+
+
+# ---- PER evaluation (csrc/ctc_decode.hip); the drivers live in seq_alignment.py ---------------------------------------
+def ctc_beam_search(probs, lengths, n_keep, blank, n_out=1):
+    """Batched CTC prefix beam search on the device: seq_alignment.beam_search_batch."""
+    from .seq_alignment import beam_search_batch
+    return beam_search_batch(probs, lengths, n_keep, blank, n_out)
+
+
+def nw_align_score(ref, ref_len, hyp, hyp_len, d=-1, m=-1, r=0, normalize=True):
+    """Batched Needleman-Wunsch score on the device (get_seq_PER by default): seq_alignment.seq_per_batch."""
+    from .seq_alignment import seq_per_batch
+    return seq_per_batch(ref, ref_len, hyp, hyp_len, d, m, r, normalize)

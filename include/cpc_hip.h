@@ -66,6 +66,8 @@ int cpc_get_mfma_mode(void);
  *                                (CTC: [0, C-1)); it was clamped for addressing and the loss is NaN
  *   CPC_DEVERR_ABX_INDEX         an ABX entry point (cpc_abx_*) met a segment id outside [0, n_seg), a segment outside the frames
  *                                or a size outside [1, S]; it was clamped for addressing and that group's score (pair's distance) is NaN
+ *   CPC_DEVERR_DECODE_RANGE      a PER entry point (cpc_ctc_beam_search, cpc_nw_align_score) met a sequence length outside
+ *                                [1, T_max] (alignment: [0, L]) or a blank outside [0, P); that sequence's score is NaN
  * The reference raises Python exceptions for such things; kernels cannot, so the wrapper (ops.check_device_errors) turns
  * the mask into a RuntimeError.  The call synchronises with the device: logging points and tests, not the step path.
  * Returns the mask (>= 0) or a negative number if the flags cannot be read. */
@@ -75,6 +77,7 @@ int cpc_get_mfma_mode(void);
 #define CPC_DEVERR_LSTM_POLL_TIMEOUT 8
 #define CPC_DEVERR_LABEL_RANGE 16
 #define CPC_DEVERR_ABX_INDEX 32
+#define CPC_DEVERR_DECODE_RANGE 64
 int cpc_device_error_flags(int clear);
 
 /* ---------------------------------------------------------------- encoder ----
@@ -369,6 +372,27 @@ int cpc_abx_pair_dtw(const float* feat, const int* seg_off, const int* seg_len, 
                      int metric, const int* pairs, int n_pairs, float* out, void* stream);
 int cpc_abx_dtw(const float* dist, const int* size1, const int* size2, int N1, int N2, int S1, int S2, int ignore_diag,
                 int symmetric, float* out, void* stream);
+
+/* ---------------------------------------------------------------- PER evaluation ----
+ * cpc/criterion/seq_alignment.py: beam_search (CTC prefix beam search) and NeedlemanWunschAlignScore, batched (csrc/ctc_decode.hip).
+ * cpc_ctc_decode_layout(B, T_max, P, n_keep, sizes): sizes[0] = bytes of the beam-search scratch, [1] = bytes of one beam's label
+ *   row, [2] / [3] = LDS bytes of the float64 / float32 search, [4] = largest n_keep, [5] = largest P, [6] = largest hypothesis
+ *   length of cpc_nw_align_score.  CPC_ERR_SHAPE for n_keep outside [1, 128] or P outside [2, 128].
+ * cpc_ctc_beam_search: probs (B, T_max, P) probabilities at element strides (stride_b, stride_t, stride_p), dtype 0 float32 /
+ *   1 float64 -- the arithmetic is the input's; lengths (B) int32 frames per sequence in [1, T_max].  One workgroup per sequence
+ *   runs beam_search(probs[b, :lengths[b]], n_keep, blank) and writes the n_out <= n_keep best beams in the reference's ranked
+ *   order: labels (B, n_out, T_max) int32 padded with -1, label_len (B, n_out), scores (B, n_out) in the input dtype, n_beams (B) =
+ *   min(n_keep, candidates of the last step); slots past n_beams have length 0 and score 0.  Bit-identical to the reference for
+ *   the same input, ties included (broken by its string key).  scratch: sizes[0] bytes (caller-owned, no initialisation).
+ * cpc_nw_align_score: out[b] = NeedlemanWunschAlignScore(ref[b, :ref_len[b]], hyp[b, :hyp_len[b]], d, m, r, normalize) in float64,
+ *   rows at element strides ref_stride / hyp_stride, ref_len in [0, L1], hyp_len in [0, L2], L2 <= sizes[6].  normalize with
+ *   ref_len 0 gives NaN (the reference divides by zero).  get_seq_PER is (d, m, r) = (-1, -1, 0), normalize 1. */
+int cpc_ctc_decode_layout(int B, int T_max, int P, int n_keep, long* sizes);
+int cpc_ctc_beam_search(const void* probs, int dtype, long stride_b, long stride_t, long stride_p, const int* lengths, int B,
+                        int T_max, int P, int blank, int n_keep, int n_out, void* scratch, long scratch_bytes, int* labels,
+                        int* label_len, void* scores, int* n_beams, void* stream);
+int cpc_nw_align_score(const int* ref, long ref_stride, const int* ref_len, int L1, const int* hyp, long hyp_stride,
+                       const int* hyp_len, int L2, int B, double d, double m, double r, int normalize, double* out, void* stream);
 
 /* ---------------------------------------------------------------- transformer layer ----
  * One TransformerLayer of cpc/transformers.py:103-111 (buildTransformerAR, :130-139), d_model 256, 8 heads,
