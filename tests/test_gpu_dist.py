@@ -202,7 +202,7 @@ def test_bench_through_the_launcher_walks_the_multi_rank_code_paths_on_one_gpu()
     16 % while the early bucket went through torch.distributed's internal stream: DESIGN.md section 5a; 1-2 % now)."""
     if not torch.cuda.is_available():
         pytest.fail("GPU test selected but no GPU visible")
-    common = ["bench.py", "--gpus", "1", "--steps", "6", "--warmup", "3", "--no-cpu-baseline", "--no-probes",
+    common = ["bench.py", "--gpus", "1", "--steps", "6", "--warmup", "3", "--full", "--no-cpu-baseline", "--no-probes",
               "--sustained-seconds", "1.0", "--launch", "eager"]
     forced = _run_bench(["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                          "--master-port", str(_free_port())] + common, {"CPC_BENCH_FORCE_DIST": "1"})
@@ -232,6 +232,20 @@ def test_bench_through_the_launcher_walks_the_multi_rank_code_paths_on_one_gpu()
         import warnings
         warnings.warn(f"data-parallel form of the step {ratio:.3f}x the plain one on this box (1.01-1.02x expected)")
     assert ratio < 1.5, (forced["sustained"], plain["sustained"])
+
+
+def test_plain_bench_line_carries_the_headline_alone():
+    """``python bench.py`` without ``--full`` times the K steps and prints the headline: none of the legs that take runs of their
+    own (sustained run, probes, in-step markers, variants, parity, CPU baseline) may run in it."""
+    if not torch.cuda.is_available():
+        pytest.fail("GPU test selected but no GPU visible")
+    line = _run_bench(["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"], {}, timeout=300)
+    assert line["metric"] == "audio-seconds/sec (train step)" and line["unit"] == "audio-s/s" and line["higher_is_better"] is True
+    assert line["steps"] == 4 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["dtype"].startswith("f32")
+    assert abs(line["value"] - 64 * 1.28 / (line["ms_per_step"] * 1e-3)) < 0.01 * line["value"]
+    full_only = {"sustained", "dist", "roofline", "roofline_hbm_layer", "roofline_scoring", "roofline_gru", "in_step_us",
+                 "time_dominant_kernel", "bf16_storage_variant", "b256_variant", "config4_variant", "parity", "cpu_baseline"}
+    assert not full_only & set(line), sorted(full_only & set(line))
 
 
 def test_bench_self_spawn_refuses_more_ranks_than_gpus():

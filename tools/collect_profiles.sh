@@ -6,8 +6,8 @@ TAG=${1:-r2}
 O=gpurun_out/profiles_$TAG
 mkdir -p $O
 export TMPDIR=/tmp
-# 1. the default bench line (probes, cpu baseline, bf16 secondary)
-timeout 400 python bench.py > $O/bench_$TAG.json 2> $O/bench.err
+# 1. the full bench line (probes, cpu baseline, bf16 secondary)
+timeout 400 python bench.py --full > $O/bench_$TAG.json 2> $O/bench.err
 # 2. kernel trace of the fp32 step (eager launch, no probes): per-kernel totals, last full step, step period
 rm -rf /tmp/prof_fp32
 timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/prof_fp32 -o res -- python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-probes --launch eager --sustained-seconds 0 > $O/bench_trace.json 2> $O/trace.err

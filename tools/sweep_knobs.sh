@@ -6,7 +6,7 @@ O=${1:-gpurun_out/r6_sweep}
 mkdir -p $O
 run() {
   label=$1; shift
-  timeout 200 python bench.py --no-cpu-baseline --no-probes --no-b256 --no-config4 --steps 30 --warmup 8 --sustained-seconds 3 "$@" 2>/dev/null | grep '^{' > $O/$label.json
+  timeout 200 python bench.py --full --no-cpu-baseline --no-probes --no-b256 --no-config4 --steps 30 --warmup 8 --sustained-seconds 3 "$@" 2>/dev/null | grep '^{' > $O/$label.json
   python - $O/$label.json "$label" <<'PY'
 import json, sys
 try:
