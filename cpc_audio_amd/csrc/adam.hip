@@ -7,6 +7,7 @@
 //   v <- b2 v + (1 - b2) g g
 //   p <- p - (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps),      bc_i = 1 - b_i^step   (computed by the host in double)
 // No weight decay, no amsgrad, no maximize: the reference uses none (train.py:335-337).
+#include "adam_common.h"
 #include "cpc_common.h"
 #include "cpc_internal.h"
 
@@ -25,14 +26,7 @@ struct AdamBatch {
     int count;
 };
 
-struct AdamCoef { float b1c, b2, b2c, step_size, inv_bc2_sqrt, eps; };
-
-__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamCoef& c) {
-    m = m + c.b1c * (g - m);
-    v = c.b2 * v + c.b2c * g * g;
-    const float denom = sqrtf(v) * c.inv_bc2_sqrt + c.eps;
-    p = p - c.step_size * m / denom;
-}
+// AdamCoef / adam_one: adam_common.h (shared with the fused probe step, probe.hip)
 
 // Capturable form (the whole train step replayed as one HIP graph: kernel arguments are frozen at capture, so nothing
 // that changes from step to step may be a host scalar): the step counter lives on the device, this one-thread kernel
@@ -102,9 +96,7 @@ extern "C" int cpc_adam_step(float* const* params, const float* const* grads, fl
                              double eps, double bias_correction1, double bias_correction2_sqrt, void* stream) {
     CPC_RETURN_IF(n < 0 || (n > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numel)), CPC_ERR_ARG);
     CPC_RETURN_IF(!(bias_correction1 > 0.) || !(bias_correction2_sqrt > 0.), CPC_ERR_ARG);
-    AdamCoef c;      // formed in double like torch does (1 - 0.999f would already be off by 1.3e-5 relative)
-    c.b1c = (float)(1. - beta1); c.b2 = (float)beta2; c.b2c = (float)(1. - beta2);
-    c.step_size = (float)(lr / bias_correction1); c.inv_bc2_sqrt = (float)(1. / bias_correction2_sqrt); c.eps = (float)eps;
+    const AdamCoef c = adam_coef_from(lr, beta1, beta2, eps, bias_correction1, bias_correction2_sqrt);
     return adam_launch(params, grads, exp_avg, exp_avg_sq, numel, n, &c, nullptr, stream);
 }
 

@@ -198,6 +198,7 @@ int nce_error_flag_fetch(int clear, unsigned* out);
 int enc_error_flag_fetch(int clear, unsigned* out);
 int lstm_error_flag_fetch(int clear, unsigned* out);
 int sup_error_flag_fetch(int clear, unsigned* out);
+int probe_error_flag_fetch(int clear, unsigned* out);      // probe.hip: the same CPC_DEVERR_LABEL_RANGE
 int abx_error_flag_fetch(int clear, unsigned* out);
 int decode_error_flag_fetch(int clear, unsigned* out);
 

@@ -1,0 +1,507 @@
+// The frozen linear-separability step (cpc/eval/linear_separability.py:21-47 with feature_maker.optimize == False) as ONE C
+// call: the linear classifier of SpeakerCriterion / PhoneCriterion on R rows of 256 frozen features, its mean cross-entropy and
+// accuracy, the gradients of W and b, and torch.optim.Adam's update of both -- two or three launches instead of the eight of
+// cpc_classifier_forward / _backward plus the optimiser's (the chain is latency-bound: DESIGN.md section 4.12).
+//
+//   probe_tile_kernel    one workgroup per (row slab, class step of 64 classes).  A tile of 32 rows of x and the step's 64 rows
+//                        of W stay in LDS.  First walk: logits -> max / argmax / sum-exp per row (-> lse, loss, hit); second
+//                        walk: the same logits again -> dlogits = (softmax - onehot) / R on the fly -> the slab's partial dW
+//                        (C x 256) and db.  Logits and dlogits never leave the chip.  Products are exact-f32 FMA chains; the
+//                        slab's loss and hit sums are float64, rows in order.
+//                        C <= 64 (the phone probe): one step, both walks in ONE launch (<kFused>).  More classes (the speaker
+//                        probe: B rows, 251 classes -- one workgroup per slab would leave the chip to one or two of them): the
+//                        first walk (<kStats>) leaves every row's statistics per step in the workspace (16 bytes per row and
+//                        step), the second (<kGrad>) merges them in step order and goes on as above.
+//   probe_update_kernel  adds the slabs' partials in slab order and applies adam_one (adam_common.h) to the element it has just
+//                        summed; its last workgroup adds the slabs' loss / hit sums and writes loss, acc and the running sums.
+//   probe_sums_kernel / probe_sums_split_kernel    (cpc_probe_eval: first walk only) loss, acc and the running sums alone.
+// cpc_probe_train_step: two launches for C <= 64, three beyond; cpc_probe_eval: two.  No float atomics, fixed orders everywhere:
+// the same bits on every run.
+#include <climits>
+
+#include "adam_common.h"
+#include "cpc_common.h"
+#include "cpc_internal.h"
+
+namespace cpc {
+
+constexpr int kPrMaxClasses = 8192;
+constexpr int kPrRows = 32;                // rows per x tile
+constexpr int kPrCls = 64;                 // classes per walk step
+constexpr int kPrLd = kC + 4;              // LDS row pitch in floats: 16-byte reads of 16 rows apart hit 16 different bank quads
+constexpr int kPrMaxSlabs = 256;
+constexpr int kPrSlabClasses = 1 << 14;    // slabs x classes: the dW partials stay <= 2^14 x 256 floats (16 MiB)
+enum { kFused = 0, kStats = 1, kGrad = 2 };
+
+// set (bit 0) by a tile that met a label outside [0, C): CPC_DEVERR_LABEL_RANGE, together with supervised.hip's word
+static __device__ unsigned g_probe_label_range = 0;
+
+struct ProbeLayout {
+    long lse, part, dbp, sums, stat, total;      // offsets in floats (sums: 2 Z doubles; stat: G x R x 4 when G > 1)
+    int Z, kchunk, G;
+};
+
+static int probe_layout(int R, int C, ProbeLayout* o) {
+    CPC_RETURN_IF(R < 1 || C < 2 || C > kPrMaxClasses, CPC_ERR_SHAPE);
+    CPC_RETURN_IF((long)R * C >= (1L << 31), CPC_ERR_SHAPE);
+    const int tiles = (R + kPrRows - 1) / kPrRows;
+    const int zmax = min(kPrMaxSlabs, max(1, kPrSlabClasses / C));
+    const int per = (tiles + zmax - 1) / zmax;
+    o->kchunk = per * kPrRows;
+    o->Z = (R + o->kchunk - 1) / o->kchunk;
+    o->lse = 0;
+    o->part = align64l(R);
+    o->dbp = o->part + align64l((long)o->Z * C * kC);
+    o->sums = o->dbp + align64l((long)o->Z * C);
+    const int nchunks = (C + kPrCls - 1) / kPrCls;       // class steps: a workgroup per (slab, step), at most ~512 in all
+    o->G = nchunks;
+    o->stat = o->sums + align64l(4L * o->Z);
+    o->total = o->stat + (o->G > 1 ? align64l(4L * o->G * R) : 0);
+    return 0;
+}
+
+struct ProbeArgs {
+    const float* x; long ldx;
+    const long long* labels;
+    const float* W; const float* b;
+    float* lse; float* part; float* dbp; double* sums; float4* stat;
+    int R, C, kchunk;
+};
+
+// Running softmax statistics of a row over the class steps met so far: maximum M at index ix (the first one on ties), S = sum
+// exp(l - M).  A step comes in as its own maximum mx at mi and e = sum exp(l - mx); a later step wins only with a larger maximum.
+__device__ __forceinline__ void probe_merge(float& M, float& S, int& ix, float mx, float e, int mi, bool first) {
+    if (first) {
+        M = mx; S = e; ix = mi;
+    } else if (mx > M) {
+        S = S * expf(M - mx) + e;
+        M = mx; ix = mi;
+    } else {
+        S += e * expf(mx - M);
+    }
+}
+
+// a row's log-sum-exp, argmax and label logit from the statistics its class steps left in stat[step * R + row]
+struct ProbeRow { float lse, ly; int ix; };
+__device__ __forceinline__ ProbeRow probe_row(const float4* __restrict__ stat, int nsteps, int R, int row, int yc) {
+    float M = 0.f, S = 1.f, ly = 0.f;
+    int ix = 0;
+    for (int s = 0; s < nsteps; ++s) {
+        const float4 st = stat[(long)s * R + row];
+        probe_merge(M, S, ix, st.x, st.y, __builtin_bit_cast(int, st.w), s == 0);
+        if (yc / kPrCls == s) ly = st.z;
+    }
+    return ProbeRow{M + logf(S), ly, ix};
+}
+
+// rows [r0, r0 + 32) of x -> xs (rows past R: zeros)
+__device__ __forceinline__ void probe_load_x(float (*xs)[kPrLd], const ProbeArgs& p, int r0) {
+    const int tid = threadIdx.x;
+    const bool vec = (((uintptr_t)p.x & 15) == 0) && ((p.ldx & 3) == 0);
+    if (vec) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int e = tid + 256 * q, r = e >> 6, k = (e & 63) * 4;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (r0 + r < p.R) v = *reinterpret_cast<const float4*>(p.x + (long)(r0 + r) * p.ldx + k);
+            *reinterpret_cast<float4*>(&xs[r][k]) = v;
+        }
+    } else {
+        for (int q = 0; q < 32; ++q) {
+            const int e = tid + 256 * q, r = e >> 8, k = e & 255;
+            xs[r][k] = r0 + r < p.R ? p.x[(long)(r0 + r) * p.ldx + k] : 0.f;
+        }
+    }
+}
+
+// classes [c0, c0 + 64) of W and b -> ws, bs (classes past C: zeros)
+__device__ __forceinline__ void probe_load_w(float (*ws)[kPrLd], float* bs, const ProbeArgs& p, int c0) {
+    const int tid = threadIdx.x;
+    const bool vec = ((uintptr_t)p.W & 15) == 0;
+    if (vec) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int e = tid + 256 * q, c = e >> 6, k = (e & 63) * 4;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (c0 + c < p.C) v = *reinterpret_cast<const float4*>(p.W + (long)(c0 + c) * kC + k);
+            *reinterpret_cast<float4*>(&ws[c][k]) = v;
+        }
+    } else {
+        for (int q = 0; q < 64; ++q) {
+            const int e = tid + 256 * q, c = e >> 8, k = e & 255;
+            ws[c][k] = c0 + c < p.C ? p.W[(long)(c0 + c) * kC + k] : 0.f;
+        }
+    }
+    if (tid < kPrCls) bs[tid] = c0 + tid < p.C ? p.b[c0 + tid] : 0.f;
+}
+
+// acc[i][j] = <x row ty + 16 i, W class tx + 16 j> + b: the k order is 0..255 for every element, in both walks
+__device__ __forceinline__ void probe_logits(const float (*xs)[kPrLd], const float (*ws)[kPrLd], const float* bs, int tx, int ty,
+                                             float (&acc)[2][4]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+    for (int k = 0; k < kC; k += 4) {
+        float4 a[2], w[4];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const float4*>(&xs[ty + 16 * i][k]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = *reinterpret_cast<const float4*>(&ws[tx + 16 * j][k]);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float s = acc[i][j];
+                s = fmaf(a[i].x, w[j].x, s);
+                s = fmaf(a[i].y, w[j].y, s);
+                s = fmaf(a[i].z, w[j].z, s);
+                s = fmaf(a[i].w, w[j].w, s);
+                acc[i][j] = s;
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] += bs[tx + 16 * j];
+}
+
+// One workgroup per (row slab blockIdx.x, class step blockIdx.y: classes [64 y, 64 y + 64)).
+//   kFused  (C <= 64, one step) both walks: statistics, then gradients
+//   kStats  the first walk; one step: the rows' results are final (cpc_probe_eval), else this step's statistics go to p.stat
+//   kGrad   (several steps) the second walk, from the rows' statistics merged over p.stat
+template <int MODE>
+__global__ __launch_bounds__(256) void probe_tile_kernel(ProbeArgs p) {
+    __shared__ float xs[kPrRows][kPrLd];
+    __shared__ float ws[kPrCls][kPrLd];
+    __shared__ float lt[kPrRows][kPrCls + 1];            // the tile's logits (first walk), dlogits (second walk)
+    __shared__ float bs[kPrCls];
+    __shared__ float row_lse[kPrRows], row_loss[kPrRows], row_hit[kPrRows];
+    __shared__ int row_y[kPrRows];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int z = blockIdx.x, step = blockIdx.y, nsteps = gridDim.y;
+    const int s0 = z * p.kchunk, s1 = min(p.R, s0 + p.kchunk);
+    const int ntiles = (s1 - s0 + kPrRows - 1) / kPrRows;
+    const int c0 = step * kPrCls, nc = min(kPrCls, p.C - c0);
+    const bool sums_here = MODE == kGrad ? step == 0 : nsteps == 1;      // does this workgroup own the slab's loss / hit sums?
+    float acc[2][4];
+    double loss_sum = 0., hit_sum = 0.;                  // thread 0: the slab's sums, rows in order
+    probe_load_w(ws, bs, p, c0);                         // (the first barrier below is in front of its readers)
+
+    // ---- first walk: per-row statistics.  Thread (sr, sq) scans classes sq, sq + 8, .. of row sr of the tile's logits.
+    const int sr = tid >> 3, sq = tid & 7;
+    for (int t = 0; MODE != kGrad && t < ntiles; ++t) {
+        const int r0 = s0 + t * kPrRows;
+        const bool live = r0 + sr < s1;
+        const long long y = live ? p.labels[r0 + sr] : 0;
+        const bool bad = y < 0 || y >= p.C;
+        const int yc = bad ? (y < 0 ? 0 : p.C - 1) : (int)y;
+        if (bad && sq == 0 && step == 0) atomicOr(&g_probe_label_range, 1u);
+        __syncthreads();                                 // the readers of xs / lt of the tile before are done
+        if (ntiles > 1 || t == 0) probe_load_x(xs, p, r0);
+        __syncthreads();
+        probe_logits(xs, ws, bs, tx, ty, acc);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) lt[ty + 16 * i][tx + 16 * j] = acc[i][j];
+        __syncthreads();
+        float mx = -INFINITY;
+        int mi = INT_MAX;
+        for (int cc = sq; cc < nc; cc += 8) {
+            const float v = lt[sr][cc];
+            if (mi == INT_MAX || v > mx) { mx = v; mi = cc; }
+        }
+#pragma unroll
+        for (int off = 1; off <= 4; off <<= 1) {
+            const float om = __shfl_xor(mx, off);
+            const int oi = __shfl_xor(mi, off);
+            if (oi != INT_MAX && (mi == INT_MAX || om > mx || (om == mx && oi < mi))) { mx = om; mi = oi; }
+        }
+        float e = 0.f;
+        for (int cc = sq; cc < nc; cc += 8) e += expf(lt[sr][cc] - mx);
+        e += __shfl_xor(e, 1);
+        e += __shfl_xor(e, 2);
+        e += __shfl_xor(e, 4);
+        const float ly = (yc >= c0 && yc < c0 + nc) ? lt[sr][yc - c0] : 0.f;
+        if (nsteps > 1) {                                // this step's statistics of the row: merged by the second walk / the sums kernel
+            if (sq == 0 && live) p.stat[(long)step * p.R + r0 + sr] = make_float4(mx, e, ly, __builtin_bit_cast(float, c0 + mi));
+            continue;
+        }
+        if (sq == 0) {
+            const float lse = mx + logf(e);
+            row_lse[sr] = lse;
+            row_y[sr] = yc;
+            row_loss[sr] = bad ? __builtin_nanf("") : lse - ly;
+            row_hit[sr] = (!bad && c0 + mi == yc) ? 1.f : 0.f;
+            if (MODE == kFused && ntiles > 1 && live) p.lse[r0 + sr] = lse;
+        }
+        __syncthreads();
+        if (tid == 0)
+            for (int r = 0; r < kPrRows && r0 + r < s1; ++r) {
+                loss_sum += (double)row_loss[r];
+                hit_sum += (double)row_hit[r];
+            }
+    }
+
+    // ---- second walk: dlogits on the fly -> the slab's dW / db partials of this step's classes.  Thread (tk, tc): columns
+    // 4 tk .. 4 tk + 3 of the 16 classes tc * 16 .. of the step.
+    if (MODE != kStats) {
+        const int tk = tid & 63, tc = tid >> 6;
+        const float g = 1.f / (float)p.R;
+        float dw[16][4];
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dw[q][e] = 0.f;
+        float dbs = 0.f;
+        for (int t = 0; t < ntiles; ++t) {
+            const int r0 = s0 + t * kPrRows;
+            __syncthreads();
+            if (ntiles > 1 || MODE == kGrad) probe_load_x(xs, p, r0);        // (kFused, one tile: xs still holds it)
+            if (MODE == kGrad) {
+                if (tid < kPrRows) {                     // the row's statistics: those of its steps, merged in step order
+                    const bool live = r0 + tid < s1;
+                    const long long y = live ? p.labels[r0 + tid] : 0;
+                    const bool bad = y < 0 || y >= p.C;
+                    const int yc = bad ? (y < 0 ? 0 : p.C - 1) : (int)y;
+                    const ProbeRow rw = live ? probe_row(p.stat, nsteps, p.R, r0 + tid, yc) : ProbeRow{0.f, 0.f, 0};
+                    row_lse[tid] = rw.lse;
+                    row_y[tid] = yc;
+                    row_loss[tid] = bad ? __builtin_nanf("") : rw.lse - rw.ly;
+                    row_hit[tid] = (!bad && rw.ix == yc) ? 1.f : 0.f;
+                }
+            } else if (ntiles > 1 && tid < kPrRows) {    // (one tile: row_lse / row_y still hold it)
+                const bool live = r0 + tid < s1;
+                const long long y = live ? p.labels[r0 + tid] : 0;
+                row_lse[tid] = live ? p.lse[r0 + tid] : 0.f;
+                row_y[tid] = y < 0 ? 0 : (y >= p.C ? p.C - 1 : (int)y);
+            }
+            __syncthreads();
+            if (MODE == kGrad && sums_here && tid == 0)
+                for (int r = 0; r < kPrRows && r0 + r < s1; ++r) {
+                    loss_sum += (double)row_loss[r];
+                    hit_sum += (double)row_hit[r];
+                }
+            probe_logits(xs, ws, bs, tx, ty, acc);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int r = ty + 16 * i;
+                const float lse = row_lse[r];
+                const int yc = row_y[r] - c0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int cc = tx + 16 * j;
+                    const bool on = r0 + r < s1 && cc < nc;
+                    lt[r][cc] = on ? g * (expf(acc[i][j] - lse) - (cc == yc ? 1.f : 0.f)) : 0.f;
+                }
+            }
+            __syncthreads();
+            for (int r = 0; r < kPrRows; ++r) {
+                const float4 xv = *reinterpret_cast<const float4*>(&xs[r][4 * tk]);
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const float d = lt[r][tc * 16 + q];
+                    dw[q][0] = fmaf(d, xv.x, dw[q][0]);
+                    dw[q][1] = fmaf(d, xv.y, dw[q][1]);
+                    dw[q][2] = fmaf(d, xv.z, dw[q][2]);
+                    dw[q][3] = fmaf(d, xv.w, dw[q][3]);
+                }
+            }
+            if (tid < kPrCls)
+                for (int r = 0; r < kPrRows; ++r) dbs += lt[r][tid];
+        }
+        float* part = p.part + (long)z * p.C * kC;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int cls = c0 + tc * 16 + q;
+            if (cls < p.C)
+                *reinterpret_cast<float4*>(part + (long)cls * kC + 4 * tk) = make_float4(dw[q][0], dw[q][1], dw[q][2], dw[q][3]);
+        }
+        if (tid < nc) p.dbp[(long)z * p.C + c0 + tid] = dbs;
+    }
+    if (sums_here && tid == 0) {
+        p.sums[2 * z] = loss_sum;
+        p.sums[2 * z + 1] = hit_sum;
+    }
+}
+
+// loss = (sum of the slabs' loss sums) / R, acc likewise, slabs in order (float64); accum[0] += loss, accum[1] += acc
+__device__ __forceinline__ void probe_finish(const double* __restrict__ sums, int Z, int R, float* __restrict__ loss,
+                                             double* __restrict__ acc, double* __restrict__ accum) {
+    double a = 0., h = 0.;
+    for (int z = 0; z < Z; ++z) {
+        a += sums[2 * z];
+        h += sums[2 * z + 1];
+    }
+    const float l = (float)(a / (double)R);
+    const double ac = h / (double)R;
+    loss[0] = l;
+    acc[0] = ac;
+    if (accum) {
+        accum[0] += (double)l;
+        accum[1] += ac;
+    }
+}
+
+__global__ __launch_bounds__(64) void probe_sums_kernel(const double* __restrict__ sums, int Z, int R, float* __restrict__ loss,
+                                                        double* __restrict__ acc, double* __restrict__ accum) {
+    if (threadIdx.x == 0) probe_finish(sums, Z, R, loss, acc, accum);
+}
+
+// cpc_probe_eval behind split first walks: every row's steps merged (step order), loss and hit summed per thread over its rows
+// (row order) and then over the threads by a fixed tree, in float64
+__global__ __launch_bounds__(256) void probe_sums_split_kernel(const float4* __restrict__ stat, const long long* __restrict__ labels,
+                                                              int G, int R, int C, float* __restrict__ loss,
+                                                              double* __restrict__ acc, double* __restrict__ accum) {
+    __shared__ double sv[256], sh[256];
+    const int tid = threadIdx.x;
+    double a = 0., h = 0.;
+    for (int r = tid; r < R; r += 256) {
+        const long long y = labels[r];
+        const bool bad = y < 0 || y >= C;
+        const int yc = bad ? (y < 0 ? 0 : C - 1) : (int)y;
+        const ProbeRow rw = probe_row(stat, G, R, r, yc);
+        a += bad ? (double)__builtin_nanf("") : (double)(rw.lse - rw.ly);
+        h += (!bad && rw.ix == yc) ? 1. : 0.;
+    }
+    sv[tid] = a;
+    sh[tid] = h;
+    __syncthreads();
+    for (int s = 128; s >= 1; s >>= 1) {
+        if (tid < s) { sv[tid] += sv[tid + s]; sh[tid] += sh[tid + s]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const float l = (float)(sv[0] / (double)R);
+        const double ac = sh[0] / (double)R;
+        loss[0] = l;
+        acc[0] = ac;
+        if (accum) {
+            accum[0] += (double)l;
+            accum[1] += ac;
+        }
+    }
+}
+
+struct ProbeUpdate {
+    const float* part; const float* dbp; const double* sums;
+    float* W; float* b; float* mW; float* vW; float* mb; float* vb;
+    float* dW_out; float* db_out;
+    float* loss; double* acc; double* accum;
+    int R, C, Z;
+};
+
+__global__ __launch_bounds__(128) void probe_update_kernel(ProbeUpdate u, AdamCoef coef) {
+    if (blockIdx.x == gridDim.x - 1) {                   // the extra workgroup: loss and accuracy
+        if (threadIdx.x == 0) probe_finish(u.sums, u.Z, u.R, u.loss, u.acc, u.accum);
+        return;
+    }
+    const long i = (long)blockIdx.x * 128 + threadIdx.x;
+    const long nw = (long)u.C * kC;
+    if (i < nw) {
+        float s = 0.f;
+        for (int z = 0; z < u.Z; ++z) s += u.part[(long)z * nw + i];
+        if (u.dW_out) u.dW_out[i] = s;
+        float pv = u.W[i], m = u.mW[i], v = u.vW[i];
+        adam_one(pv, s, m, v, coef);
+        u.W[i] = pv; u.mW[i] = m; u.vW[i] = v;
+    } else if (i < nw + u.C) {
+        const long c = i - nw;
+        float s = 0.f;
+        for (int z = 0; z < u.Z; ++z) s += u.dbp[(long)z * u.C + c];
+        if (u.db_out) u.db_out[c] = s;
+        float pv = u.b[c], m = u.mb[c], v = u.vb[c];
+        adam_one(pv, s, m, v, coef);
+        u.b[c] = pv; u.mb[c] = m; u.vb[c] = v;
+    }
+}
+
+int probe_error_flag_fetch(int clear, unsigned* out) {
+    unsigned v = 0;
+    if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_probe_label_range), sizeof(v)) != hipSuccess) return CPC_ERR_ARG;
+    if (clear && v) {
+        const unsigned zero = 0;
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_probe_label_range), &zero, sizeof(zero)) != hipSuccess) return CPC_ERR_ARG;
+    }
+    *out = v;
+    return 0;
+}
+
+static ProbeArgs probe_args(const float* x, long ldx, const long long* labels, const float* W, const float* b, float* ws,
+                            const ProbeLayout& ly, int R, int C) {
+    ProbeArgs p;
+    p.x = x; p.ldx = ldx; p.labels = labels; p.W = W; p.b = b;
+    p.lse = ws + ly.lse; p.part = ws + ly.part; p.dbp = ws + ly.dbp;
+    p.sums = reinterpret_cast<double*>(ws + ly.sums);
+    p.stat = reinterpret_cast<float4*>(ws + ly.stat);
+    p.R = R; p.C = C; p.kchunk = ly.kchunk;
+    return p;
+}
+
+}  // namespace cpc
+
+using namespace cpc;
+
+extern "C" int cpc_probe_layout(int R, int C, long* sizes) {
+    CPC_RETURN_IF(!sizes, CPC_ERR_ARG);
+    ProbeLayout ly;
+    const int rc = probe_layout(R, C, &ly);
+    if (rc) return rc;
+    sizes[0] = ly.total;
+    sizes[1] = ly.Z;
+    sizes[2] = ly.kchunk;
+    return 0;
+}
+
+extern "C" int cpc_probe_train_step(const float* x, long ldx, const long long* labels, int R, int C, float* W, float* b,
+                                    float* exp_avg_W, float* exp_avg_sq_W, float* exp_avg_b, float* exp_avg_sq_b, double lr,
+                                    double beta1, double beta2, double eps, double bias_correction1,
+                                    double bias_correction2_sqrt, float* workspace, float* loss, double* acc, double* accum,
+                                    float* dW_out, float* db_out, void* stream) {
+    ProbeLayout ly;
+    const int rc = probe_layout(R, C, &ly);
+    if (rc) return rc;
+    CPC_RETURN_IF(!x || ldx < kC || !labels || !W || !b || !exp_avg_W || !exp_avg_sq_W || !exp_avg_b || !exp_avg_sq_b, CPC_ERR_ARG);
+    CPC_RETURN_IF(!workspace || ((uintptr_t)workspace & 15) || !loss || !acc, CPC_ERR_ARG);
+    CPC_RETURN_IF(!(bias_correction1 > 0.) || !(bias_correction2_sqrt > 0.), CPC_ERR_ARG);
+    const hipStream_t st = (hipStream_t)stream;
+    const ProbeArgs p = probe_args(x, ldx, labels, W, b, workspace, ly, R, C);
+    if (ly.G == 1) {
+        hipLaunchKernelGGL(probe_tile_kernel<kFused>, dim3(ly.Z), dim3(256), 0, st, p);
+        CPC_LAUNCH_CHECK();
+    } else {
+        hipLaunchKernelGGL(probe_tile_kernel<kStats>, dim3(ly.Z, ly.G), dim3(256), 0, st, p);
+        CPC_LAUNCH_CHECK();
+        hipLaunchKernelGGL(probe_tile_kernel<kGrad>, dim3(ly.Z, ly.G), dim3(256), 0, st, p);
+        CPC_LAUNCH_CHECK();
+    }
+    ProbeUpdate u;
+    u.part = p.part; u.dbp = p.dbp; u.sums = p.sums;
+    u.W = W; u.b = b; u.mW = exp_avg_W; u.vW = exp_avg_sq_W; u.mb = exp_avg_b; u.vb = exp_avg_sq_b;
+    u.dW_out = dW_out; u.db_out = db_out;
+    u.loss = loss; u.acc = acc; u.accum = accum;
+    u.R = R; u.C = C; u.Z = ly.Z;
+    const AdamCoef coef = adam_coef_from(lr, beta1, beta2, eps, bias_correction1, bias_correction2_sqrt);
+    const long n = (long)C * kC + C;
+    hipLaunchKernelGGL(probe_update_kernel, dim3((unsigned)((n + 127) / 128) + 1), dim3(128), 0, st, u, coef);
+    CPC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cpc_probe_eval(const float* x, long ldx, const long long* labels, int R, int C, const float* W, const float* b,
+                              float* workspace, float* loss, double* acc, double* accum, void* stream) {
+    ProbeLayout ly;
+    const int rc = probe_layout(R, C, &ly);
+    if (rc) return rc;
+    CPC_RETURN_IF(!x || ldx < kC || !labels || !W || !b, CPC_ERR_ARG);
+    CPC_RETURN_IF(!workspace || ((uintptr_t)workspace & 15) || !loss || !acc, CPC_ERR_ARG);
+    const hipStream_t st = (hipStream_t)stream;
+    const ProbeArgs p = probe_args(x, ldx, labels, W, b, workspace, ly, R, C);
+    hipLaunchKernelGGL(probe_tile_kernel<kStats>, dim3(ly.Z, ly.G), dim3(256), 0, st, p);
+    CPC_LAUNCH_CHECK();
+    if (ly.G == 1) hipLaunchKernelGGL(probe_sums_kernel, dim3(1), dim3(64), 0, st, p.sums, ly.Z, R, loss, acc, accum);
+    else hipLaunchKernelGGL(probe_sums_split_kernel, dim3(1), dim3(256), 0, st, p.stat, labels, ly.G, R, C, loss, acc, accum);
+    CPC_LAUNCH_CHECK();
+    return 0;
+}

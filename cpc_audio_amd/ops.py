@@ -673,6 +673,67 @@ class CtcXentFunction(torch.autograd.Function):
         return (None if dx is None else dx.view(B, S, _HID)), None, dW, db
 
 
+# ---- the frozen linear-separability step in one C call (csrc/probe.hip) ------------------------------------------------
+_probe_workspaces = {}
+
+
+def _probe_setup(x, label, weight, what):
+    _require_cuda(x, what)
+    x, ldx = _rows_of(x, what)
+    R, C = x.shape[0], weight.shape[0]
+    label = _labels_on(label, x.device).view(-1)
+    if label.numel() != R:
+        raise ValueError(f"{what}: {label.numel()} labels for {R} feature rows")
+    lib = _lib.get()
+    stream = _stream()
+    key = (R, C, x.device, stream)
+    ws = _probe_workspaces.get(key)
+    if ws is None:                                       # once per shape (and stream: calls on one stream are ordered)
+        sizes = _layout("probe_layout", lib.cpc_probe_layout, 3, R, C)
+        ws = _probe_workspaces[key] = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
+    return lib, x, ldx, label, R, C, ws, stream
+
+
+def _probe_outputs(x, out):
+    if out is not None:
+        return out
+    return (torch.empty(1, 1, device=x.device, dtype=torch.float32), torch.empty(1, 1, device=x.device, dtype=torch.float64))
+
+
+@torch.no_grad()
+def probe_train_step(x, label, weight, bias, optimizer, accum=None, out=None, grads=None):
+    """One frozen probe step (cpc_probe_train_step): x (R,256) (any row stride), label (R,) -> loss (1,1) float32 and acc (1,1)
+    float64 of nn.Linear(weight, bias) + mean cross-entropy BEFORE the update, and ``optimizer`` (optim.Adam)'s update of
+    weight and bias in place, moments and step count included.  accum: two device doubles that receive += loss, += acc;
+    out: (loss, acc) tensors to write instead of new ones; grads: (dW, db) tensors that receive the gradients."""
+    lib, x, ldx, label, R, C, ws, stream = _probe_setup(x, label, weight, "probe_train_step")
+    for p in (weight, bias):
+        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+            raise TypeError("probe_train_step: dense fp32 parameters on the GPU expected")
+    group, moments, bc1, bc2s = optimizer.fused_step_state([weight, bias])
+    (mW, vW), (mb, vb) = moments
+    loss, acc = _probe_outputs(x, out)
+    dW, db = grads if grads is not None else (None, None)
+    beta1, beta2 = group["betas"]
+    with torch.cuda.device(x.device):
+        lib.check(lib.cpc_probe_train_step(x.data_ptr(), ldx, _p(label), R, C, _p(weight), _p(bias), _p(mW), _p(vW), _p(mb),
+                                           _p(vb), float(group["lr"]), beta1, beta2, float(group["eps"]), bc1, bc2s, _p(ws),
+                                           _p(loss), _p(acc), _p(accum), _p(dW), _p(db), stream), "probe_train_step")
+    return loss, acc
+
+
+@torch.no_grad()
+def probe_eval(x, label, weight, bias, accum=None, out=None):
+    """Loss (1,1) float32 and accuracy (1,1) float64 of the linear classifier on x (R,256), label (R,) (cpc_probe_eval);
+    accum / out as in probe_train_step."""
+    lib, x, ldx, label, R, C, ws, stream = _probe_setup(x, label, weight, "probe_eval")
+    loss, acc = _probe_outputs(x, out)
+    with torch.cuda.device(x.device):
+        lib.check(lib.cpc_probe_eval(x.data_ptr(), ldx, _p(label), R, C, _p(weight.detach().contiguous()),
+                                     _p(bias.detach().contiguous()), _p(ws), _p(loss), _p(acc), _p(accum), stream), "probe_eval")
+    return loss, acc
+
+
 def candidate_destinations(ext, B, S, K):
     """(perm, row_ptr) for cpc_nce_backward: the B*W*(N+K) candidate slots sorted (stably) by the
     row of z.view(B*S,256) their gradient lands on.  ext: (B,W,N) int32 negative rows; the K

@@ -117,6 +117,38 @@ class Adam(torch.optim.Adam):
                     self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"] = m, v
             self._device_step.fill_(k)
 
+    def fused_step_state(self, params):
+        """For a kernel that applies this optimiser's update itself (ops.probe_train_step): hands out the moment tensors of
+        ``params`` -- created zeroed as step() creates them -- and advances their shared step count by one.
+        -> (their parameter group, [(exp_avg, exp_avg_sq) per parameter], bias_correction1, bias_correction2_sqrt), the
+        corrections computed in double as step() computes them.  After n such calls state_dict() is what it would be after
+        n step() calls on the same parameters."""
+        if self._device_step is not None:
+            raise RuntimeError("fused_step_state(): not available in device_step_counter() mode")
+        self._flush_fast()
+        group = next((g for g in self.param_groups if any(q is params[0] for q in g["params"])), None)
+        if group is None or not all(any(q is p for q in group["params"]) for p in params):
+            raise ValueError("fused_step_state(): the parameters must belong to one parameter group of this optimiser")
+        if not self._group_ok(group):
+            raise ValueError("fused_step_state(): weight decay, amsgrad, maximize and tensor learning rates are not supported")
+        steps, moments = set(), []
+        for p in params:
+            st = self.state[p]
+            if len(st) == 0:
+                st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if st["step"].is_cuda:                          # a state loaded from a fused / capturable torch Adam
+                st["step"] = st["step"].cpu()
+            st["step"] += 1
+            steps.add(int(st["step"].item()))
+            moments.append((st["exp_avg"], st["exp_avg_sq"]))
+        if len(steps) != 1:
+            raise ValueError("fused_step_state(): the parameters do not share one step count")
+        k = steps.pop()
+        beta1, beta2 = group["betas"]
+        return group, moments, 1.0 - beta1 ** k, math.sqrt(1.0 - beta2 ** k)
+
     def _tables(self, group, params):
         """ctypes pointer tables of one launch, cached while the same (parameter, gradient) OBJECTS come back -- the train
         loops keep their gradients in one persistent flat buffer (train.Trainer), so this is every step after the first."""

@@ -346,6 +346,32 @@ int cpc_ctc_forward(const float* x, const float* W, const float* b, const long l
                     int S, int C, void* stream);
 int cpc_ctc_backward(const float* saved, const float* dloss, float* dlogits, int B, int S, int C, void* stream);
 
+/* ------------------------------------------------------- fused linear-probe step ----
+ * The frozen step of cpc/eval/linear_separability.py (train_step :21-47 with feature_maker.optimize == False, val_step :50-68)
+ * for SpeakerCriterion / PhoneCriterion: logits = x W^T + b on R rows of 256 features, the mean cross-entropy, the accuracy
+ * (argmax == label, the first index on ties), dW and db of the mean loss and torch.optim.Adam's update of W and b, in one call
+ * (csrc/probe.hip): cpc_probe_train_step enqueues two kernels for C <= 64 and three beyond, cpc_probe_eval two.  Logits and
+ * dlogits stay on the chip; for C > 64 the workspace takes 16 bytes of softmax statistics per row and 64 classes.
+ * Exact-f32 FMA products, float64 loss / hit sums, no float atomics and fixed summation orders: identical calls give identical
+ * bits.  Nothing is allocated, nothing waits for the device, arguments are checked before any launch.
+ * cpc_probe_layout(R, C, sizes): 2 <= C <= 8192, R >= 1, R * C < 2^31 (CPC_ERR_SHAPE beyond).  sizes[0] = workspace floats,
+ *   sizes[1] = row slabs (workgroups of the tile kernel), sizes[2] = rows per slab.
+ * x: row r at x + r * ldx (ldx >= 256: cFeature[:, -1, :] is read in place); labels: int64 (R).  A label outside [0, C) is clamped
+ *   for addressing, raises CPC_DEVERR_LABEL_RANGE and makes that call's loss NaN.
+ * workspace: sizes[0] floats, 16-byte aligned; contents are scratch.  loss: one float; acc: one double; accum (or NULL): two
+ *   doubles, accum[0] += loss, accum[1] += acc (the epoch's running sums: no host read per step).
+ * cpc_probe_train_step: W (C,256), b (C) and their moments exp_avg_* / exp_avg_sq_* are updated in place with the element-wise
+ *   arithmetic of cpc_adam_step (same scalars: bias_correction1 = 1 - beta1^step, bias_correction2_sqrt = sqrt(1 - beta2^step));
+ *   dW_out (C,256) / db_out (C), when non-NULL, receive the gradients the update was made from.  The loss is that of W, b
+ *   BEFORE the update. */
+int cpc_probe_layout(int R, int C, long* sizes);
+int cpc_probe_train_step(const float* x, long ldx, const long long* labels, int R, int C, float* W, float* b, float* exp_avg_W,
+                         float* exp_avg_sq_W, float* exp_avg_b, float* exp_avg_sq_b, double lr, double beta1, double beta2,
+                         double eps, double bias_correction1, double bias_correction2_sqrt, float* workspace, float* loss,
+                         double* acc, double* accum, float* dW_out, float* db_out, void* stream);
+int cpc_probe_eval(const float* x, long ldx, const long long* labels, int R, int C, const float* W, const float* b,
+                   float* workspace, float* loss, double* acc, double* accum, void* stream);
+
 /* ---------------------------------------------------------------- ABX evaluation ----
  * cpc/eval/ABX.py and cpc/eval/ABX/{abx_group_computation.py, dtw.pyx}: frame distances, normalised DTW and the per-group
  * score 1 - theta of get_theta_group_dtw, batched over a whole pass (csrc/abx.hip).
