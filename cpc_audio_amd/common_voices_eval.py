@@ -15,9 +15,11 @@ PER: perStep decodes a whole batch with seq_alignment.beam_search_batch (beams o
 seq_alignment.seq_per_batch on the device -- no host round trip in between, no process pool -- and accumulates the mean and
 sqrt(E[x^2] - mean^2) in float64 in loader order.
 
-Torch GPU ops, not the hot path: the classifier's Conv1d (k 8, stride 4), its optional LSTM, seqNorm and nn.CTCLoss.  CPC
-checkpoints load as abx.py loads them (checkpoint_args.json next to the checkpoint, harness.load_checkpoint); their encoder and
-autoregressor run on the package's HIP kernels.
+The classifier's head and loss -- Conv1d (k 8, stride 4) on 256 features, log_softmax and nn.CTCLoss with the utterances'
+lengths -- run on csrc/phone_head.hip (ops.PhoneHeadCtcFunction, ops.phone_head_logits; `--hipHead` / `--no-hipHead`, see
+CTCphone_criterion).  Torch GPU ops, not the hot path: seqNorm, the optional LSTM and Dropout2d in front of the head, and the
+whole classifier for another feature width or kernel size.  CPC checkpoints load as abx.py loads them (checkpoint_args.json
+next to the checkpoint, harness.load_checkpoint); their encoder and autoregressor run on the package's HIP kernels.
 """
 import argparse
 import json
@@ -33,10 +35,12 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
+from . import ops
 from . import seq_alignment as SA
 from .dataset import filterSeqs, findAllSeqs, loadFile, parseSeqLabels
 
 N_KEEP = 20           # perStep's beams
+HIP_HEAD_DEFAULT = True   # what CTCphone_criterion(hipHead=None) means where the HIP head applies
 
 
 def load(path_item):
@@ -111,11 +115,23 @@ def ctc_input_lengths(size_seq, downsampling_factor):
 
 class CTCphone_criterion(torch.nn.Module):
     """The reference's phone classifier: optional 1-layer LSTM (conv1), Conv1d(dim, nPhones + 1, sizeKernel, stride
-    sizeKernel // 2), nn.CTCLoss(blank=nPhones, zero_infinity=True).  Same state-dict keys.  Torch GPU ops.  getPrediction
-    takes the per-utterance feature lengths (sizeSeq // downsampling) and does not write into its input."""
+    sizeKernel // 2), nn.CTCLoss(blank=nPhones, zero_infinity=True).  Same state-dict keys.  getPrediction takes the
+    per-utterance feature lengths (sizeSeq // downsampling) and does not write into its input.
 
-    def __init__(self, dimEncoder, nPhones, LSTM=False, sizeKernel=8, seqNorm=False, dropout=False, reduction='sum'):
+    hipHead: the Conv1d, log_softmax and the CTC loss on csrc/phone_head.hip (seqNorm, the LSTM and the dropout stay torch ops).
+    That path takes dimEncoder 256, sizeKernel 8, CUDA fp32 features and what cpc_phone_head_layout accepts.  None: use it
+    where it applies (HIP_HEAD_DEFAULT), torch elsewhere; False: torch; True: the HIP path or NotImplementedError.  On it
+    getPrediction is not differentiable (evaluation); forward is.  last_path names the path of the last call."""
+
+    def __init__(self, dimEncoder, nPhones, LSTM=False, sizeKernel=8, seqNorm=False, dropout=False, reduction='sum',
+                 hipHead=None):
         super().__init__()
+        self.hipHead = hipHead
+        self._hipConfig = dimEncoder == 256 and sizeKernel == ops.PHONE_HEAD_KERNEL
+        if hipHead and not self._hipConfig:
+            raise NotImplementedError("CTCphone_criterion(hipHead=True): the HIP phone head is built for dimEncoder 256 and "
+                                      f"sizeKernel 8 (got {dimEncoder}, {sizeKernel})")
+        self.last_path = None
         self.seqNorm = seqNorm
         self.epsilon = 1e-8
         self.dropout = torch.nn.Dropout2d(p=0.5, inplace=False) if dropout else None
@@ -126,7 +142,42 @@ class CTCphone_criterion(torch.nn.Module):
         self.BLANK_LABEL = nPhones
         self.useLSTM = LSTM
 
+    def _hipPath(self, cFeature, Lmax=0):
+        """Does this call run on the HIP head?"""
+        if self.hipHead is False or (self.hipHead is None and not HIP_HEAD_DEFAULT) or not self._hipConfig:
+            return False
+        B, S, _ = cFeature.size()
+        ok = cFeature.is_cuda and cFeature.dtype == torch.float32 and \
+            ops.phone_head_supported(B, S, self.BLANK_LABEL + 1, Lmax)
+        if self.hipHead and not ok:
+            raise NotImplementedError("CTCphone_criterion(hipHead=True): the HIP phone head takes CUDA fp32 features of a shape "
+                                      f"cpc_phone_head_layout accepts (got {tuple(cFeature.size())}, {cFeature.dtype}, "
+                                      f"{cFeature.device}, {Lmax} target columns)")
+        return ok
+
+    def _hipFeatures(self, cFeature, featureSize):
+        """What the head reads, channels-last: seqNorm, the LSTM and the dropout as getPrediction applies them."""
+        B, S, H = cFeature.size()
+        if self.seqNorm:
+            rows = []
+            for b in range(B):
+                size = int(featureSize[b])
+                m = cFeature[b, :size].mean(dim=0, keepdim=True)
+                v = cFeature[b, :size].var(dim=0, keepdim=True)
+                rows.append((cFeature[b] - m) / torch.sqrt(v + self.epsilon))
+            cFeature = torch.stack(rows)
+        if self.useLSTM:
+            cFeature = self.conv1(cFeature)[0]
+        if self.dropout is not None:
+            cFeature = self.dropout(cFeature.permute(0, 2, 1)).permute(0, 2, 1)
+        return cFeature
+
     def getPrediction(self, cFeature, featureSize):
+        if self._hipPath(cFeature):
+            self.last_path = "hip"
+            head = self.PhoneCriterionClassifier
+            return ops.phone_head_logits(self._hipFeatures(cFeature, featureSize), head.weight, head.bias)
+        self.last_path = "torch"
         B, S, H = cFeature.size()
         if self.seqNorm:
             rows = []
@@ -146,6 +197,17 @@ class CTCphone_criterion(torch.nn.Module):
 
     def forward(self, cFeature, featureSize, label, labelSize):
         """featureSize: sizeSeq // downsampling per utterance (integer tensor)."""
+        if self._hipPath(cFeature, label.size(1)):
+            # the lengths do cut_data's work on the device: no .max() round trip, no copies
+            self.last_path = "hip"
+            head = self.PhoneCriterionClassifier
+            nWindows = (cFeature.size(1) - ops.PHONE_HEAD_KERNEL) // ops.PHONE_HEAD_STRIDE + 1
+            loss = ops.PhoneHeadCtcFunction.apply(self._hipFeatures(cFeature, featureSize), head.weight, head.bias,
+                                                  torch.clamp(featureSize // 4, max=nWindows), label, labelSize,
+                                                  self.BLANK_LABEL, self.lossCriterion.reduction).view(1, -1)
+            if torch.isinf(loss).sum() > 0 or torch.isnan(loss).sum() > 0:
+                loss = loss.new_zeros(1, 1).requires_grad_()
+            return loss
         predictions = self.getPrediction(cFeature, featureSize)
         featureSize = featureSize // 4
         predictions = cut_data(predictions, featureSize)
@@ -301,6 +363,7 @@ def get_PER_args(args):
     args.dropout = data.get("dropout", False)
     args.in_dim = data.get("in_dim", 1)
     args.loss_reduction = data.get("loss_reduction", "mean")
+    args.hipHead = data.get("hipHead", None)
     return args
 
 
@@ -331,6 +394,9 @@ def parse_args(argv):
     t.add_argument('--dropout', action='store_true')
     t.add_argument('--in_dim', type=int, default=1, help='Dimension of the input data')
     t.add_argument('--loss_reduction', type=str, default='mean', choices=['mean', 'sum'])
+    t.add_argument('--hipHead', dest='hipHead', action='store_true', default=None,
+                   help="The classifier's head and CTC loss on the HIP kernels (an error where they do not apply)")
+    t.add_argument('--no-hipHead', dest='hipHead', action='store_false', help="The classifier's head and CTC loss as torch ops")
     p = sub.add_parser('per')
     p.add_argument('output', type=str)
     p.add_argument('--batchSize', type=int, default=8)
@@ -412,7 +478,7 @@ def _main(args):
     feature_maker, hidden_gar, downsampling_factor = load_feature_maker(args.pathCheckpoint, args.no_pretraining, args.in_dim)
     feature_maker.cuda()
     phone_criterion = CTCphone_criterion(hidden_gar, n_phones, args.LSTM, seqNorm=args.seqNorm, dropout=args.dropout,
-                                         reduction=args.loss_reduction).cuda()
+                                         reduction=args.loss_reduction, hipHead=args.hipHead).cuda()
     print(f"Loading the validation dataset at {args.pathDB}")
     dataset_val = SingleSequenceDataset(args.pathDB, seq_val, phone_labels, inDim=args.in_dim)
     val_loader = DataLoader(dataset_val, batch_size=args.batchSize, shuffle=True)

@@ -62,6 +62,9 @@ def check_device_errors(clear=True):
         what.append("an ABX plan named a segment or size out of range (it was clamped; that score is NaN)")
     if mask & 64:
         what.append("a PER decode or alignment received a length outside its row or a blank outside [0, P) (that score is NaN)")
+    if mask & 128:
+        what.append("the phone classifier's CTC loss received an input or target length outside its range (it was clamped; that "
+                    "sequence's loss is NaN)")
     if what:
         raise _lib.CpcHipError("device-side error: " + "; ".join(what))
 
@@ -671,6 +674,113 @@ class CtcXentFunction(torch.autograd.Function):
             lib.check(lib.cpc_ctc_backward(_p(saved), _p(dloss.contiguous()), _p(dlogits), B, S, C, _stream()), "ctc_backward")
             dx, dW, db = _classifier_backward(x, _HID, weight, None, None, None, dlogits, B * S, C, ctx.needs_input_grad[0])
         return (None if dx is None else dx.view(B, S, _HID)), None, dW, db
+
+
+# ---- the PER phone classifier (csrc/phone_head.hip) ----------------------------------------------------------------------
+PHONE_HEAD_KERNEL, PHONE_HEAD_STRIDE = 8, 4
+_CTC_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
+
+
+def phone_head_layout(B, S, C, Lmax=0):
+    """(T, wr floats, scratch floats, logits floats, CTC saved floats) of cpc_phone_head_layout; ValueError for a shape the
+    kernels do not take."""
+    return _layout("phone_head_layout", _lib.get().cpc_phone_head_layout, 5, int(B), int(S), int(C), int(Lmax))
+
+
+def phone_head_supported(B, S, C, Lmax=0):
+    try:
+        phone_head_layout(B, S, C, Lmax)
+    except ValueError:
+        return False
+    return True
+
+
+def _phone_head_inputs(x, weight, what):
+    _require_cuda(x, what)
+    if x.dim() != 3 or x.shape[2] != _HID or weight.dim() != 3 or tuple(weight.shape[1:]) != (_HID, PHONE_HEAD_KERNEL):
+        raise NotImplementedError(f"cpc_audio_amd.{what}: the HIP phone head is built for (B, S, 256) features and a "
+                                  "(C, 256, 8) weight")
+    return x.contiguous()
+
+
+def _phone_head_forward(x, weight, bias, sizes):
+    lib = _lib.get()
+    B, S, _ = x.shape
+    C = weight.shape[0]
+    wr = torch.empty(sizes[1], device=x.device, dtype=torch.float32)
+    scratch = torch.empty(sizes[2], device=x.device, dtype=torch.float32)
+    logits = torch.empty(B, sizes[0], C, device=x.device, dtype=torch.float32)
+    lib.check(lib.cpc_phone_head_forward(_p(x), _p(weight), _p(bias), _p(wr), _p(scratch), _p(logits), B, S, C, _stream()),
+              "phone_head_forward")
+    return logits, wr
+
+
+def phone_head_logits(x, weight, bias):
+    """x (B, S, 256) channels-last, weight (C, 256, 8), bias (C) -> logits (B, (S - 8) // 4 + 1, C): nn.Conv1d(256, C, 8,
+    stride 4) of the permuted features, permuted back.  Not differentiable (evaluation: val_step, perStep)."""
+    x = _phone_head_inputs(x.detach(), weight, "phone_head_logits")
+    weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
+    with torch.cuda.device(x.device):
+        sizes = phone_head_layout(x.shape[0], x.shape[1], weight.shape[0])
+        return _phone_head_forward(x, weight, bias, sizes)[0]
+
+
+class PhoneHeadCtcFunction(torch.autograd.Function):
+    """x (B, S, 256), weight (C, 256, 8), bias (C), in_len (B) int64 windows per utterance, targets (B, Lmax) int64 padded,
+    tgt_len (B) int64, blank, reduction -> loss (1,) float32 ((B,) for 'none'): nn.Conv1d(256, C, 8, stride 4), log_softmax
+    and nn.CTCLoss(blank, reduction, zero_infinity=True).  Lengths and targets stay on the device.  x receives a gradient
+    only when it requires one."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, in_len, targets, tgt_len, blank, reduction):
+        x = _phone_head_inputs(x, weight, "PhoneHeadCtcFunction")
+        lib = _lib.get()
+        B, S, _ = x.shape
+        C = weight.shape[0]
+        red = _CTC_REDUCTIONS[reduction]
+        targets = targets.to(x.device, non_blocking=True)
+        if targets.dtype != torch.int64:
+            targets = targets.to(torch.int64)
+        if targets.dim() != 2 or targets.shape[0] != B:
+            raise ValueError(f"PhoneHeadCtcFunction: targets of shape {tuple(targets.shape)} for {B} utterances")
+        Lmax = targets.shape[1]
+        if Lmax and targets.stride(1) != 1:
+            targets = targets.contiguous()
+        in_len, tgt_len = _labels_on(in_len, x.device).view(-1), _labels_on(tgt_len, x.device).view(-1)
+        if in_len.numel() != B or tgt_len.numel() != B:
+            raise ValueError(f"PhoneHeadCtcFunction: {in_len.numel()} input and {tgt_len.numel()} target lengths for {B} utterances")
+        weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
+        with torch.cuda.device(x.device):
+            sizes = phone_head_layout(B, S, C, Lmax)
+            T = sizes[0]
+            logits, wr = _phone_head_forward(x, weight, bias, sizes)
+            saved = torch.empty(sizes[4], device=x.device, dtype=torch.float32)
+            loss = torch.empty(B if red == 0 else 1, device=x.device, dtype=torch.float32)
+            lib.check(lib.cpc_ctc_seq_forward(_p(logits), _p(in_len), targets.data_ptr() if Lmax else None,
+                                              targets.stride(0) if Lmax else 0, _p(tgt_len), _p(saved), _p(loss), B, T, C, Lmax,
+                                              int(blank), red, _stream()), "ctc_seq_forward")
+        ctx.save_for_backward(x, wr, logits, saved)
+        ctx.dims = (B, S, T, C, Lmax, int(blank), red, sizes[2])
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        x, wr, logits, saved = ctx.saved_tensors
+        B, S, T, C, Lmax, blank, red, nscr = ctx.dims
+        if dloss is None:
+            return (None,) * 8
+        lib = _lib.get()
+        with torch.cuda.device(x.device):
+            dlogits = torch.empty_like(logits)
+            lib.check(lib.cpc_ctc_seq_backward(_p(logits), _p(saved), _p(dloss.contiguous()), _p(dlogits), B, T, C, Lmax, blank,
+                                               red, _stream()), "ctc_seq_backward")
+            scratch = torch.empty(nscr, device=x.device, dtype=torch.float32)
+            dW = torch.empty(C, _HID, PHONE_HEAD_KERNEL, device=x.device, dtype=torch.float32)
+            db = torch.empty(C, device=x.device, dtype=torch.float32)
+            dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+            lib.check(lib.cpc_phone_head_backward(_p(x), _p(wr), _p(dlogits), _p(scratch), _p(dW), _p(db), _p(dx), B, S, C,
+                                                  _stream()), "phone_head_backward")
+        return dx, dW, db, None, None, None, None, None
 
 
 # ---- the frozen linear-separability step in one C call (csrc/probe.hip) ------------------------------------------------

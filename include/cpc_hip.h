@@ -63,11 +63,14 @@ int cpc_get_mfma_mode(void);
  *   CPC_DEVERR_LSTM_POLL_TIMEOUT a workgroup of the persistent LSTM recurrence (cpc_lstm_forward / _backward) gave up
  *                                waiting for another one; its outputs carry NaN from that step on
  *   CPC_DEVERR_LABEL_RANGE       a supervised criterion (cpc_classifier_forward, cpc_ctc_forward) met a label outside [0, C)
- *                                (CTC: [0, C-1)); it was clamped for addressing and the loss is NaN
+ *                                (CTC: [0, C-1)); it was clamped for addressing and the loss is NaN.  cpc_ctc_seq_forward: a
+ *                                target outside [0, C) or equal to the blank; that sequence's loss is NaN
  *   CPC_DEVERR_ABX_INDEX         an ABX entry point (cpc_abx_*) met a segment id outside [0, n_seg), a segment outside the frames
  *                                or a size outside [1, S]; it was clamped for addressing and that group's score (pair's distance) is NaN
  *   CPC_DEVERR_DECODE_RANGE      a PER entry point (cpc_ctc_beam_search, cpc_nw_align_score) met a sequence length outside
  *                                [1, T_max] (alignment: [0, L]) or a blank outside [0, P); that sequence's score is NaN
+ *   CPC_DEVERR_LENGTH_RANGE      cpc_ctc_seq_forward met an input length outside [0, T] or a target length outside [0, Lmax];
+ *                                it was clamped for addressing and that sequence's loss is NaN
  * The reference raises Python exceptions for such things; kernels cannot, so the wrapper (ops.check_device_errors) turns
  * the mask into a RuntimeError.  The call synchronises with the device: logging points and tests, not the step path.
  * Returns the mask (>= 0) or a negative number if the flags cannot be read. */
@@ -78,6 +81,7 @@ int cpc_get_mfma_mode(void);
 #define CPC_DEVERR_LABEL_RANGE 16
 #define CPC_DEVERR_ABX_INDEX 32
 #define CPC_DEVERR_DECODE_RANGE 64
+#define CPC_DEVERR_LENGTH_RANGE 128
 int cpc_device_error_flags(int clear);
 
 /* ---------------------------------------------------------------- encoder ----
@@ -345,6 +349,40 @@ int cpc_classifier_backward(const float* x, long ldx, const float* W, const long
 int cpc_ctc_forward(const float* x, const float* W, const float* b, const long long* labels, float* saved, float* loss, int B,
                     int S, int C, void* stream);
 int cpc_ctc_backward(const float* saved, const float* dloss, float* dlogits, int B, int S, int C, void* stream);
+
+/* ------------------------------------------------------- PER phone classifier ----
+ * CTCphone_criterion of cpc/eval/common_voices_eval.py: nn.Conv1d(256, C, 8, stride 4) on the features, log_softmax and
+ * nn.CTCLoss(blank, reduction, zero_infinity = True) with per-utterance input lengths and padded targets (csrc/phone_head.hip).
+ * fp32 storage, exact-f32 FMA products, CTC recursions in float64 in log space, no float atomics and fixed summation orders:
+ * identical calls give identical bits, and a sequence's results do not depend on the batch around it.  Arguments are checked
+ * before any launch; nothing is allocated and nothing waits for the device.
+ * cpc_phone_head_layout(B, S, C, Lmax, sizes): B >= 1 utterances of S >= 8 frames, T = (S - 8) / 4 + 1 <= 2048 windows,
+ *   2 <= C <= 256 classes, 0 <= Lmax <= 512 target columns, B * T * C < 2^28 (CPC_ERR_SHAPE beyond).  sizes[0] = T,
+ *   sizes[1] = floats of wr (C * 2048), sizes[2] = scratch floats of the head's forward and backward, sizes[3] = floats of
+ *   logits / dlogits (B * T * C), sizes[4] = saved floats of cpc_ctc_seq_forward.
+ * x: (B, S, 256) contiguous, channels-last (cFeature before its permute); W (C, 256, 8) and dW in torch's Conv1d layout; b (C).
+ * cpc_phone_head_forward: logits[b, t, o] = b[o] + sum_{j<8} sum_{c<256} x[b, 4t + j, c] W[o, c, j], (B, T, C) dense.  wr receives
+ *   the weight in the order of a window's 2048 floats, wr[o][j * 256 + c]: the backward's dX reads it.
+ * cpc_phone_head_backward: dlogits (B, T, C) -> dW, db overwritten, summed over row slabs in slab order; dX (B, S, 256) only
+ *   when non-NULL, in gather form (each frame sums its at most two windows; frames no window covers get exactly 0).
+ * cpc_ctc_seq_forward: logits (B, T, C); in_len (B) int64 in [0, T]; targets int64, row b at targets + b * tgt_stride
+ *   (tgt_stride >= Lmax; may be NULL when Lmax = 0); tgt_len (B) int64 in [0, Lmax]; 0 <= blank < C; reduction 0 none (loss: B
+ *   floats), 1 mean (the mean over b of loss_b / max(tgt_len_b, 1)), 2 sum.  A sequence whose loss is infinite (its target does
+ *   not fit into in_len, in_len = 0 with a target) counts 0; in_len = 0 with an empty target is loss 0.  A target outside
+ *   [0, C) or equal to the blank raises CPC_DEVERR_LABEL_RANGE, a length out of range CPC_DEVERR_LENGTH_RANGE; either is clamped
+ *   for addressing and makes that sequence's loss NaN.
+ * cpc_ctc_seq_backward: dlogits (B, T, C) of the reduced loss, scaled by dloss (one float; B floats for reduction none):
+ *   exactly 0 for t >= in_len[b] and for a sequence whose loss was infinite.  Same logits, saved and sizes as the forward. */
+int cpc_phone_head_layout(int B, int S, int C, int Lmax, long* sizes);
+int cpc_phone_head_forward(const float* x, const float* W, const float* b, float* wr, float* scratch, float* logits, int B,
+                           int S, int C, void* stream);
+int cpc_phone_head_backward(const float* x, const float* wr, const float* dlogits, float* scratch, float* dW, float* db,
+                            float* dX, int B, int S, int C, void* stream);
+int cpc_ctc_seq_forward(const float* logits, const long long* in_len, const long long* targets, long tgt_stride,
+                        const long long* tgt_len, float* saved, float* loss, int B, int T, int C, int Lmax, int blank,
+                        int reduction, void* stream);
+int cpc_ctc_seq_backward(const float* logits, const float* saved, const float* dloss, float* dlogits, int B, int T, int C,
+                         int Lmax, int blank, int reduction, void* stream);
 
 /* ------------------------------------------------------- fused linear-probe step ----
  * The frozen step of cpc/eval/linear_separability.py (train_step :21-47 with feature_maker.optimize == False, val_step :50-68)

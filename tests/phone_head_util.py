@@ -1,0 +1,110 @@
+"""Shared by the phone-head tests: seeded cases, the float64 CPU oracle (F.conv1d, F.log_softmax, F.ctc_loss) and the calls
+through the C ABI (the emulator library on the CPU, the product library on the GPU)."""
+import ctypes
+
+import torch
+import torch.nn.functional as F
+
+H = 256
+NONE, MEAN, SUM = 0, 1, 2
+REDUCTION = {"none": NONE, "mean": MEAN, "sum": SUM}
+LABEL_RANGE, LENGTH_RANGE = 16, 128          # CPC_DEVERR_*
+
+
+def P(t):
+    return None if t is None else t.data_ptr()
+
+
+def layout(lib, B, S, C, Lmax):
+    sizes = (ctypes.c_long * 5)()
+    assert lib.cpc_phone_head_layout(B, S, C, Lmax, sizes) == 0
+    return tuple(sizes)          # T, wr floats, scratch floats, logits floats, ctc saved floats
+
+
+def frames_for(T):
+    """A frame count whose window count is T."""
+    return 4 * T + 4
+
+
+def head_case(B, S, C, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, S, H, generator=g)
+    W = 0.05 * torch.randn(C, H, 8, generator=g)
+    b = 0.1 * torch.randn(C, generator=g)
+    return x, W, b
+
+
+def ragged_targets(B, Lmax, n_phones, seed, lengths=None):
+    """Padded (B, Lmax) int64 targets in [0, n_phones) and their lengths (given, or seeded in [1, Lmax])."""
+    g = torch.Generator().manual_seed(seed)
+    tgt = torch.randint(0, n_phones, (B, max(Lmax, 1)), generator=g)[:, :Lmax]
+    tl = torch.randint(1, Lmax + 1, (B,), generator=g) if lengths is None else torch.tensor(lengths, dtype=torch.long)
+    return tgt.contiguous(), tl
+
+
+def oracle_head(x, W, b, dlogits=None):
+    """float64 logits (B, T, C) of F.conv1d and, with dlogits, (dW, db, dX)."""
+    xr, Wr, br = (t.double().clone().requires_grad_(True) for t in (x, W, b))
+    logits = F.conv1d(xr.permute(0, 2, 1), Wr, br, stride=4).permute(0, 2, 1)
+    if dlogits is None:
+        return logits.detach()
+    (logits * dlogits.double()).sum().backward()
+    return logits.detach(), Wr.grad, br.grad, xr.grad
+
+
+def oracle_ctc(logits, in_len, targets, tgt_len, blank, reduction, dloss=None):
+    """float64: (loss, dlogits) of log_softmax + F.ctc_loss(zero_infinity=True); dloss scales the loss (per sequence for 'none')."""
+    lg = logits.double().clone().requires_grad_(True)
+    lp = F.log_softmax(lg, dim=2).permute(1, 0, 2)
+    loss = F.ctc_loss(lp, targets, in_len, tgt_len, blank=blank, reduction=reduction, zero_infinity=True)
+    w = torch.ones_like(loss) if dloss is None else dloss.double().view_as(loss)
+    (loss * w).sum().backward()
+    return loss.detach(), lg.grad
+
+
+def oracle_full(x, W, b, in_len, targets, tgt_len, blank, reduction):
+    """float64 end to end: (loss, logits, dW, db, dX)."""
+    xr, Wr, br = (t.double().clone().requires_grad_(True) for t in (x, W, b))
+    logits = F.conv1d(xr.permute(0, 2, 1), Wr, br, stride=4).permute(0, 2, 1)
+    lp = F.log_softmax(logits, dim=2).permute(1, 0, 2)
+    loss = F.ctc_loss(lp, targets, in_len, tgt_len, blank=blank, reduction=reduction, zero_infinity=True)
+    loss.sum().backward()
+    return loss.detach(), logits.detach(), Wr.grad, br.grad, xr.grad
+
+
+def run_head(lib, x, W, b, dlogits=None, need_dx=True, canary=0, fill=7.0):
+    """cpc_phone_head_forward (+ _backward with dlogits) on host tensors; outputs carry `canary` spare floats."""
+    B, S, _ = x.shape
+    C = W.shape[0]
+    T, wr_n, scr_n, lg_n, _ = layout(lib, B, S, C, 0)
+    wr = torch.full((wr_n + canary,), fill)
+    scratch = torch.full((scr_n + canary,), float("nan"))
+    logits = torch.full((lg_n + canary,), fill)
+    assert lib.cpc_phone_head_forward(P(x), P(W), P(b), P(wr), P(scratch), P(logits), B, S, C, None) == 0
+    out = dict(T=T, wr=wr, scratch=scratch, logits=logits, n=dict(wr=wr_n, scratch=scr_n, logits=lg_n, dW=C * H * 8, db=C,
+                                                                 dX=B * S * H))
+    if dlogits is not None:
+        dW = torch.full((C * H * 8 + canary,), fill)
+        db = torch.full((C + canary,), fill)
+        dX = torch.full((B * S * H + canary,), fill) if need_dx else None
+        assert lib.cpc_phone_head_backward(P(x), P(wr), P(dlogits), P(scratch), P(dW), P(db), P(dX), B, S, C, None) == 0
+        out.update(dW=dW, db=db, dX=dX)
+    return out
+
+
+def run_ctc(lib, logits, in_len, targets, tgt_len, blank, reduction, dloss=None, canary=0, fill=7.0):
+    """cpc_ctc_seq_forward + _backward on host tensors -> (loss, dlogits, saved), each with `canary` spare floats."""
+    B, T, C = logits.shape
+    Lmax = targets.shape[1]
+    red = REDUCTION[reduction]
+    _, _, _, lg_n, saved_n = layout(lib, B, frames_for(T), C, Lmax)
+    saved = torch.full((saved_n + canary,), float("nan"))
+    n_loss = B if red == NONE else 1
+    loss = torch.full((n_loss + canary,), fill)
+    logits = logits.contiguous()
+    assert lib.cpc_ctc_seq_forward(P(logits), P(in_len), P(targets) if Lmax else None, targets.stride(0) if Lmax else 0,
+                                   P(tgt_len), P(saved), P(loss), B, T, C, Lmax, blank, red, None) == 0
+    dloss = torch.ones(n_loss) if dloss is None else dloss.float().contiguous()
+    dl = torch.full((lg_n + canary,), fill)
+    assert lib.cpc_ctc_seq_backward(P(logits), P(saved), P(dloss), P(dl), B, T, C, Lmax, blank, red, None) == 0
+    return loss, dl, saved

@@ -1,0 +1,123 @@
+"""One training step of the PER phone classifier on the GPU, HIP head against torch ops: one JSON line per run.
+
+CTCphone_criterion(256, 40) on B = 8 utterances of S = 1000 frames (10 s), 41 classes, targets of 60 labels, frozen features
+(no dX): forward + backward of `criterion(c_feature, sizes, phones, sizePhones).mean()`, as common_voices_eval.train_step runs
+it.  hipHead=True is csrc/phone_head.hip (ops.PhoneHeadCtcFunction); hipHead=False is the module's torch code: Conv1d,
+log_softmax, nn.CTCLoss with its cut_data round trips.  Both modules hold the same weights and are timed in one process,
+alternating, after a warm-up of every shape: device events around each step, median of --reps (>= 5).  Also reported: the
+forward alone under no_grad (val_step) and the same step with features that require a gradient.  Kernel resources come from
+tools/kernel_resources.py.
+
+    python tools/bench_phone_head.py [--reps 9] [--out profiles/phone_head_bench.json]
+"""
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from cpc_audio_amd import common_voices_eval as CV, ops    # noqa: E402
+
+
+def one(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def timed_pair(fns, reps, warmup=3):
+    """Median ms of each callable, the callables alternating inside every repetition."""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ms[k].append(one(fn))
+    return {k: round(sorted(v)[len(v) // 2], 4) for k, v in ms.items()}, {k: [round(x, 4) for x in v] for k, v in ms.items()}
+
+
+def resources():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"),
+                        os.path.join(ROOT, "cpc_audio_amd", "csrc", "phone_head.hip")], capture_output=True, text=True)
+    return [re.sub(r"\s+", " ", line.strip()) for line in r.stdout.splitlines() if "kernel" in line]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--B", type=int, default=8)
+    ap.add_argument("--S", type=int, default=1000)
+    ap.add_argument("--phones", type=int, default=40)
+    ap.add_argument("--labels", type=int, default=60)
+    ap.add_argument("--out", type=str, default=None)
+    args = ap.parse_args()
+    if args.reps < 5:
+        ap.error("--reps must be at least 5")
+    B, S, n_phones, L = args.B, args.S, args.phones, args.labels
+    torch.manual_seed(0)
+    crits = {"hip": CV.CTCphone_criterion(256, n_phones, reduction="mean", hipHead=True).cuda(),
+             "torch": CV.CTCphone_criterion(256, n_phones, reduction="mean", hipHead=False).cuda()}
+    crits["torch"].load_state_dict(crits["hip"].state_dict())
+    g = torch.Generator().manual_seed(1)
+    x = torch.randn(B, S, 256, generator=g).cuda()
+    x_grad = x.clone().requires_grad_(True)
+    sizes = torch.full((B,), S, dtype=torch.long, device="cuda")
+    phones = torch.randint(0, n_phones, (B, L), generator=g).cuda()
+    size_phones = torch.full((B,), L, dtype=torch.long, device="cuda")
+    last = {}
+
+    def step(name, feats):
+        crit = crits[name]
+
+        def fn():
+            for p in crit.parameters():
+                p.grad = None
+            feats.grad = None
+            loss = crit(feats, sizes, phones, size_phones)
+            loss.mean().backward()
+            last[name] = loss.detach()
+        return fn
+
+    def forward(name):
+        crit = crits[name]
+
+        def fn():
+            with torch.no_grad():
+                last[name + "_fwd"] = crit(x, sizes, phones, size_phones)
+        return fn
+
+    frozen, frozen_all = timed_pair({k: step(k, x) for k in crits}, args.reps)
+    paths = {k: c.last_path for k, c in crits.items()}
+    assert paths == {"hip": "hip", "torch": "torch"}, paths
+    grads = {k: [p.grad.clone() for p in (c.PhoneCriterionClassifier.weight, c.PhoneCriterionClassifier.bias)]
+             for k, c in crits.items()}
+    with_dx, _ = timed_pair({k: step(k, x_grad) for k in crits}, args.reps)
+    fwd, _ = timed_pair({k: forward(k) for k in crits}, args.reps)
+    ops.check_device_errors()
+    # the two paths compute the same step (fp32 against fp32: both carry their own rounding)
+    agree = {"loss_hip": float(last["hip"]), "loss_torch": float(last["torch"]),
+             "dW_rel_diff": float((grads["hip"][0] - grads["torch"][0]).norm() / grads["torch"][0].norm()),
+             "db_rel_diff": float((grads["hip"][1] - grads["torch"][1]).norm() / grads["torch"][1].norm())}
+    result = {"bench": "phone_head_step", "device": torch.cuda.get_device_name(0), "B": B, "S": S, "classes": n_phones + 1,
+              "labels": L, "windows": (S - 8) // 4 + 1, "reps": args.reps,
+              "step_frozen_ms": frozen, "step_frozen_all_ms": frozen_all, "step_with_dx_ms": with_dx, "forward_ms": fwd,
+              "speedup_frozen": round(frozen["torch"] / frozen["hip"], 3), "agreement": agree, "resources": resources()}
+    print(json.dumps(result))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
