@@ -130,6 +130,7 @@ SIGNATURES = {
     "cpc_probe_layout": (_I, [_I, _I, _P]),
     "cpc_probe_train_step": (_I, [_P, _L, _P, _I, _I] + [_P] * 6 + [ctypes.c_double] * 6 + [_P] * 7),
     "cpc_probe_eval": (_I, [_P, _L, _P, _I, _I] + [_P] * 7),
+    "cpc_posterior_forward": (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _P, _P]),
     "cpc_abx_layout": (_I, [_I, _I, _I, _L, _P]),
     "cpc_abx_group_scores": (_I, [_P, _P, _P, _I, _L, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P]),
     "cpc_abx_pair_dtw": (_I, [_P, _P, _P, _I, _L, _I, _I, _I, _P, _I, _P, _P]),

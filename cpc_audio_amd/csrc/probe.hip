@@ -17,18 +17,14 @@
 //   probe_sums_kernel / probe_sums_split_kernel    (cpc_probe_eval: first walk only) loss, acc and the running sums alone.
 // cpc_probe_train_step: two launches for C <= 64, three beyond; cpc_probe_eval: two.  No float atomics, fixed orders everywhere:
 // the same bits on every run.
-#include <climits>
-
 #include "adam_common.h"
 #include "cpc_common.h"
 #include "cpc_internal.h"
+#include "probe_tile.h"
 
 namespace cpc {
 
-constexpr int kPrMaxClasses = 8192;
-constexpr int kPrRows = 32;                // rows per x tile
-constexpr int kPrCls = 64;                 // classes per walk step
-constexpr int kPrLd = kC + 4;              // LDS row pitch in floats: 16-byte reads of 16 rows apart hit 16 different bank quads
+// (the tile itself -- kPrRows x kPrCls, its loaders, probe_logits, probe_row_stats, probe_merge -- is probe_tile.h's)
 constexpr int kPrMaxSlabs = 256;
 constexpr int kPrSlabClasses = 1 << 14;    // slabs x classes: the dW partials stay <= 2^14 x 256 floats (16 MiB)
 enum { kFused = 0, kStats = 1, kGrad = 2 };
@@ -68,19 +64,6 @@ struct ProbeArgs {
     int R, C, kchunk;
 };
 
-// Running softmax statistics of a row over the class steps met so far: maximum M at index ix (the first one on ties), S = sum
-// exp(l - M).  A step comes in as its own maximum mx at mi and e = sum exp(l - mx); a later step wins only with a larger maximum.
-__device__ __forceinline__ void probe_merge(float& M, float& S, int& ix, float mx, float e, int mi, bool first) {
-    if (first) {
-        M = mx; S = e; ix = mi;
-    } else if (mx > M) {
-        S = S * expf(M - mx) + e;
-        M = mx; ix = mi;
-    } else {
-        S += e * expf(mx - M);
-    }
-}
-
 // a row's log-sum-exp, argmax and label logit from the statistics its class steps left in stat[step * R + row]
 struct ProbeRow { float lse, ly; int ix; };
 __device__ __forceinline__ ProbeRow probe_row(const float4* __restrict__ stat, int nsteps, int R, int row, int yc) {
@@ -92,78 +75,6 @@ __device__ __forceinline__ ProbeRow probe_row(const float4* __restrict__ stat, i
         if (yc / kPrCls == s) ly = st.z;
     }
     return ProbeRow{M + logf(S), ly, ix};
-}
-
-// rows [r0, r0 + 32) of x -> xs (rows past R: zeros)
-__device__ __forceinline__ void probe_load_x(float (*xs)[kPrLd], const ProbeArgs& p, int r0) {
-    const int tid = threadIdx.x;
-    const bool vec = (((uintptr_t)p.x & 15) == 0) && ((p.ldx & 3) == 0);
-    if (vec) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int e = tid + 256 * q, r = e >> 6, k = (e & 63) * 4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r0 + r < p.R) v = *reinterpret_cast<const float4*>(p.x + (long)(r0 + r) * p.ldx + k);
-            *reinterpret_cast<float4*>(&xs[r][k]) = v;
-        }
-    } else {
-        for (int q = 0; q < 32; ++q) {
-            const int e = tid + 256 * q, r = e >> 8, k = e & 255;
-            xs[r][k] = r0 + r < p.R ? p.x[(long)(r0 + r) * p.ldx + k] : 0.f;
-        }
-    }
-}
-
-// classes [c0, c0 + 64) of W and b -> ws, bs (classes past C: zeros)
-__device__ __forceinline__ void probe_load_w(float (*ws)[kPrLd], float* bs, const ProbeArgs& p, int c0) {
-    const int tid = threadIdx.x;
-    const bool vec = ((uintptr_t)p.W & 15) == 0;
-    if (vec) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int e = tid + 256 * q, c = e >> 6, k = (e & 63) * 4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (c0 + c < p.C) v = *reinterpret_cast<const float4*>(p.W + (long)(c0 + c) * kC + k);
-            *reinterpret_cast<float4*>(&ws[c][k]) = v;
-        }
-    } else {
-        for (int q = 0; q < 64; ++q) {
-            const int e = tid + 256 * q, c = e >> 8, k = e & 255;
-            ws[c][k] = c0 + c < p.C ? p.W[(long)(c0 + c) * kC + k] : 0.f;
-        }
-    }
-    if (tid < kPrCls) bs[tid] = c0 + tid < p.C ? p.b[c0 + tid] : 0.f;
-}
-
-// acc[i][j] = <x row ty + 16 i, W class tx + 16 j> + b: the k order is 0..255 for every element, in both walks
-__device__ __forceinline__ void probe_logits(const float (*xs)[kPrLd], const float (*ws)[kPrLd], const float* bs, int tx, int ty,
-                                             float (&acc)[2][4]) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-    for (int k = 0; k < kC; k += 4) {
-        float4 a[2], w[4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const float4*>(&xs[ty + 16 * i][k]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = *reinterpret_cast<const float4*>(&ws[tx + 16 * j][k]);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float s = acc[i][j];
-                s = fmaf(a[i].x, w[j].x, s);
-                s = fmaf(a[i].y, w[j].y, s);
-                s = fmaf(a[i].z, w[j].z, s);
-                s = fmaf(a[i].w, w[j].w, s);
-                acc[i][j] = s;
-            }
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] += bs[tx + 16 * j];
 }
 
 // One workgroup per (row slab blockIdx.x, class step blockIdx.y: classes [64 y, 64 y + 64)).
@@ -206,23 +117,9 @@ __global__ __launch_bounds__(256) void probe_tile_kernel(ProbeArgs p) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) lt[ty + 16 * i][tx + 16 * j] = acc[i][j];
         __syncthreads();
-        float mx = -INFINITY;
-        int mi = INT_MAX;
-        for (int cc = sq; cc < nc; cc += 8) {
-            const float v = lt[sr][cc];
-            if (mi == INT_MAX || v > mx) { mx = v; mi = cc; }
-        }
-#pragma unroll
-        for (int off = 1; off <= 4; off <<= 1) {
-            const float om = __shfl_xor(mx, off);
-            const int oi = __shfl_xor(mi, off);
-            if (oi != INT_MAX && (mi == INT_MAX || om > mx || (om == mx && oi < mi))) { mx = om; mi = oi; }
-        }
-        float e = 0.f;
-        for (int cc = sq; cc < nc; cc += 8) e += expf(lt[sr][cc] - mx);
-        e += __shfl_xor(e, 1);
-        e += __shfl_xor(e, 2);
-        e += __shfl_xor(e, 4);
+        float mx, e;
+        int mi;
+        probe_row_stats(lt, sr, sq, nc, mx, mi, e);
         const float ly = (yc >= c0 && yc < c0 + nc) ? lt[sr][yc - c0] : 0.f;
         if (nsteps > 1) {                                // this step's statistics of the row: merged by the second walk / the sums kernel
             if (sq == 0 && live) p.stat[(long)step * p.R + r0 + sr] = make_float4(mx, e, ly, __builtin_bit_cast(float, c0 + mi));

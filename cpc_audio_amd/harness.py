@@ -16,6 +16,10 @@ CUDA-only ``cpc/train.py`` script:
   * ``FeatureModule`` / ``build_feature`` cpc/feature_loader.py:15-38, :221-269 (chunked inference with
                                          carried GRU state), taking a waveform tensor instead of a file path
                                          (torchaudio is not part of this environment).
+  * ``ModelPhoneCombined`` / ``loadSupervisedCriterion`` / ``loadModel`` / ``toOneHot``
+                                         cpc/feature_loader.py:41-97, :156-190, :212-218: a feature maker followed by a
+                                         trained phone classifier (one HIP call: csrc/posterior.hip) and the loaders of both,
+                                         for build_zeroSpeech_features.
 
 Differences by design: logs are accumulated ON DEVICE and synchronised once per ``logging_step`` instead of
 a device->host copy every step (train.py:98-99); multi-GPU is one process per GPU with one SUM all-reduce
@@ -368,11 +372,148 @@ class FeatureModule(torch.nn.Module):
         return out.reshape(-1, out.size(2)) if self.collapse else out
 
 
+def toOneHot(inputVector, nItems):
+    """cpc/feature_loader.py:212-218: (B, S) indices -> (B, S, nItems) int64 one-hot."""
+    batchSize, seqSize = inputVector.size()
+    out = torch.zeros((batchSize, seqSize, nItems), device=inputVector.device, dtype=torch.long)
+    out.scatter_(2, inputVector.view(batchSize, seqSize, 1), 1)
+    return out
+
+
+POSTERIOR_HIP_DEFAULT = True   # what ModelPhoneCombined(hipHead=None) means where the HIP call applies (DESIGN.md section 4.13)
+
+
+class ModelPhoneCombined(torch.nn.Module):
+    """cpc/feature_loader.py:41-71: a feature maker followed by a phone classifier.  ``forward(data)`` returns the (B, S, P)
+    float posteriors softmax(criterion.getPrediction(model(data)), dim=2) or, with ``oneHot``, the int64 one-hot of their argmax.
+
+    hipHead: classifier, softmax / argmax and one-hot as one HIP call (ops.posterior, csrc/posterior.hip).  That path takes a
+    PhoneCriterion whose classifier is a single nn.Linear, or a CTCPhoneCriterion, with 256 input features and 2..8192 classes,
+    and CUDA fp32 features with unit last stride.  None: use it where it applies (POSTERIOR_HIP_DEFAULT), torch elsewhere;
+    False: torch; True: the HIP call or NotImplementedError.  Evaluation only: the HIP path is not differentiable.
+    ``last_path`` names the path of the last call ("hip" / "torch")."""
+
+    def __init__(self, model, criterion, oneHot, hipHead=None):
+        super().__init__()
+        self.model, self.criterion, self.oneHot, self.hipHead = model, criterion, oneHot, hipHead
+        self.last_path = None
+
+    @property
+    def collapse(self):                                   # (build_feature asks the module it is given for this ...
+        return getattr(self.model, "collapse", False)
+
+    @property
+    def featureMaker(self):                               # ... and for its network: does the autoregressor carry its state?)
+        return getattr(self.model, "featureMaker", None)
+
+    def getDownsamplingFactor(self):
+        return self.model.getDownsamplingFactor()
+
+    def _hipLinear(self, c):
+        """The nn.Linear the HIP call applies to ``c``, or None."""
+        from .criterion import CTCPhoneCriterion, PhoneCriterion
+        if self.hipHead is False or (self.hipHead is None and not POSTERIOR_HIP_DEFAULT):
+            return None
+        lin = getattr(self.criterion, "PhoneCriterionClassifier", None)
+        ok = isinstance(self.criterion, (PhoneCriterion, CTCPhoneCriterion)) and isinstance(lin, torch.nn.Linear) \
+            and lin.in_features == 256 and 2 <= lin.out_features <= ops.POSTERIOR_MAX_CLASSES \
+            and c.dim() == 3 and c.size(2) == 256 and c.is_cuda and c.dtype == torch.float32 and c.stride(2) == 1 \
+            and lin.weight.device == c.device
+        if self.hipHead and not ok:
+            raise NotImplementedError("ModelPhoneCombined(hipHead=True): the HIP posterior call takes a single-nn.Linear "
+                                      "PhoneCriterion or a CTCPhoneCriterion on 256 features with 2..8192 classes and CUDA fp32 "
+                                      f"features (got {type(self.criterion).__name__}, {tuple(c.size())}, {c.dtype}, {c.device})")
+        return lin if ok else None
+
+    def forward(self, data):
+        c_feature = self.model(data)
+        lin = self._hipLinear(c_feature)
+        if lin is not None:
+            self.last_path = "hip"
+            B, S, H = c_feature.size()
+            rows = c_feature.reshape(B * S, H)            # (a view wherever the frames are evenly strided)
+            return ops.posterior(rows, lin.weight, lin.bias, one_hot=self.oneHot).view(B, S, -1)
+        self.last_path = "torch"
+        pred = self.criterion.getPrediction(c_feature)
+        if self.oneHot:
+            return toOneHot(pred.argmax(dim=2), pred.size(2))
+        return torch.nn.functional.softmax(pred, dim=2)
+
+
+def _checkpoint_args(path_checkpoint):
+    with open(os.path.join(os.path.dirname(path_checkpoint), "checkpoint_args.json")) as f:
+        return json.load(f)
+
+
+def loadSupervisedCriterion(pathCheckpoint):
+    """cpc/feature_loader.py:83-97: -> (criterion, nPhones), the phone classifier saved in ``pathCheckpoint`` by
+    train --supervised or by linear_separability.  The flags come from the checkpoint_args.json beside it -- ``CTC`` and
+    ``onEncoder`` (linear_separability writes ``get_encoded``) --, the feature width and the class count from the saved
+    classifier's weight (with CTC one class is the blank: nPhones = C - 1).  Unlike the reference, the labels file the
+    classifier was trained on is not read again."""
+    from .criterion import CTCPhoneCriterion, PhoneCriterion
+    saved = _checkpoint_args(pathCheckpoint)
+    state = torch.load(pathCheckpoint, map_location="cpu")["cpcCriterion"]
+    weight = None if state is None else state.get("PhoneCriterionClassifier.weight")
+    if weight is None:
+        raise ValueError(f"{pathCheckpoint}: its criterion state holds no PhoneCriterionClassifier.weight -- not a single-layer "
+                         "phone classifier")
+    n_classes, dim = weight.shape
+    on_encoder = bool(saved.get("onEncoder", saved.get("get_encoded", False)))
+    if saved.get("CTC", False):
+        nPhones = n_classes - 1
+        criterion = CTCPhoneCriterion(dim, nPhones, on_encoder)
+    else:
+        nPhones = n_classes
+        criterion = PhoneCriterion(dim, nPhones, on_encoder)
+    criterion.load_state_dict(state)
+    return criterion, nPhones
+
+
+def _architecture_args(path):
+    """The saved arguments that describe the network of checkpoint ``path``: those beside it, or -- when they carry a ``load``
+    entry into another directory -- those of the checkpoint it was built on (cpc/feature_loader.py:163-170)."""
+    saved = _checkpoint_args(path)
+    load = saved.get("load")
+    if load is not None and (len(load) > 1 or os.path.dirname(load[0]) != os.path.dirname(path)):
+        if len(load) > 1:
+            raise ValueError(f"{path}: concatenated models (more than one checkpoint) are not supported")
+        return _architecture_args(load[0])
+    return saved
+
+
+def loadModel(pathCheckpoints):
+    """cpc/feature_loader.py:156-190 for ONE checkpoint: -> (model, hiddenGar, hiddenEncoder).  When the saved arguments carry
+    a ``load`` entry that points into another directory (a classifier trained on top of a CPC checkpoint), the architecture is
+    read from THAT directory's checkpoint_args.json; the state dict is loaded (strict=False) from the path given.  Arguments
+    missing from the file take the reference's defaults (cpc_default_config.py); the autoregressor carries its state from
+    call to call when samplingType is "sequential", as getAR builds it.  Concatenated models -- more than one checkpoint at
+    either level -- raise ValueError."""
+    from .train import build_model
+    if len(pathCheckpoints) != 1:
+        raise ValueError("concatenated models (more than one checkpoint) are not supported")
+    path = pathCheckpoints[0]
+    print(f"Loading checkpoint {path}")
+    saved = _architecture_args(path)
+    hiddenEncoder, arMode = saved.get("hiddenEncoder", 256), saved.get("arMode", "LSTM")
+    hiddenGar = hiddenEncoder if arMode == "transformer" else saved.get("hiddenGar", 256)
+    model = build_model(hiddenEncoder=hiddenEncoder, hiddenGar=hiddenGar, nLevelsGRU=saved.get("nLevelsGRU", 1),
+                        keepHidden=saved.get("samplingType", "samespeaker") == "sequential",
+                        reverse=saved.get("cpc_mode") == "reverse", arMode=arMode, sizeWindow=saved.get("sizeWindow", 20480),
+                        abspos=saved.get("abspos", False))
+    print(f"Loading the state dict at {path}")
+    model.load_state_dict(torch.load(path, map_location="cpu")["gEncoder"], strict=False)
+    return model, hiddenGar, hiddenEncoder
+
+
 def seq_normalization(out):
     """Zero mean / unit (unbiased) variance along the time axis of (B, frames, dim) features, eps 1e-8 under the root
-    (cpc/feature_loader.py:221-225)."""
-    var, mean = torch.var_mean(out, dim=1, keepdim=True)
-    return (out - mean) * torch.rsqrt(var + 1e-08)
+    (cpc/feature_loader.py:221-225) -- in the reference's own sequence of operations (mean, var, subtract, root, divide), so that
+    a text export of normalised features (build_zeroSpeech_features --seqNorm) has the reference's digits; a fused var_mean and a
+    reciprocal root round the last bit differently."""
+    mean = out.mean(dim=1, keepdim=True)
+    var = out.var(dim=1, keepdim=True)
+    return (out - mean) / torch.sqrt(var + 1e-08)
 
 
 def chunk_plan(n_samples, max_size_seq, strict, downsampling):

@@ -844,6 +844,32 @@ def probe_eval(x, label, weight, bias, accum=None, out=None):
     return loss, acc
 
 
+# ---- phone posteriors for feature export (csrc/posterior.hip) -----------------------------------------------------------
+POSTERIOR_MAX_CLASSES = 8192
+
+
+@torch.no_grad()
+def posterior(x, weight, bias, one_hot=False):
+    """softmax(x weight^T + bias) per row -- float32 (R, C) -- or, with ``one_hot``, the int64 (R, C) one-hot of each row's
+    argmax (the first index on ties), in one launch (cpc_posterior_forward).  x: CUDA fp32 (R, 256) with any row stride;
+    runs on the current stream.  Evaluation only: not differentiable."""
+    _require_cuda(x, "posterior")
+    x, ldx = _rows_of(x, "posterior")
+    R, C = x.shape[0], weight.shape[0]
+    weight, bias = weight.detach(), bias.detach()
+    if tuple(weight.shape) != (C, _HID) or tuple(bias.shape) != (C,):
+        raise ValueError(f"posterior: weight (C, 256) and bias (C,) expected, got {tuple(weight.shape)} and {tuple(bias.shape)}")
+    for t in (weight, bias):
+        if t.device != x.device or t.dtype != torch.float32:
+            raise TypeError("posterior: fp32 parameters on the features' device expected")
+    out = torch.empty(R, C, device=x.device, dtype=torch.int64 if one_hot else torch.float32)
+    lib = _lib.get()
+    with torch.cuda.device(x.device):
+        lib.check(lib.cpc_posterior_forward(x.data_ptr(), ldx, _p(weight.contiguous()), _p(bias.contiguous()), R, C,
+                                            1 if one_hot else 0, _p(out), None, _stream()), "posterior_forward")
+    return out
+
+
 def candidate_destinations(ext, B, S, K):
     """(perm, row_ptr) for cpc_nce_backward: the B*W*(N+K) candidate slots sorted (stably) by the
     row of z.view(B*S,256) their gradient lands on.  ext: (B,W,N) int32 negative rows; the K

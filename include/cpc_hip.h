@@ -410,6 +410,19 @@ int cpc_probe_train_step(const float* x, long ldx, const long long* labels, int 
 int cpc_probe_eval(const float* x, long ldx, const long long* labels, int R, int C, const float* W, const float* b,
                    float* workspace, float* loss, double* acc, double* accum, void* stream);
 
+/* ------------------------------------------------------------ phone posteriors ----
+ * What cpc/feature_loader.py:61-71 (ModelPhoneCombined.forward) computes behind the feature maker: the linear classifier of
+ * PhoneCriterion / CTCPhoneCriterion on R rows of 256 features, then softmax -- or argmax and one-hot -- in one launch
+ * (csrc/posterior.hip).  The x tile of 32 rows is read once and kept in LDS while the classes are walked 64 at a time; logits
+ * and unnormalised values never leave the chip, there is no workspace, and every element of out is stored exactly once.
+ * Exact-f32 MFMA products, fixed orders, no atomics: identical calls give identical bits.  Arguments are checked before the launch.
+ * 2 <= C <= 8192, R >= 1, R * C < 2^31 (CPC_ERR_SHAPE beyond).  x: row r at x + r * ldx (ldx >= 256; pointers and strides that are
+ * not 16-byte aligned are read with scalar loads); W (C,256), b (C).
+ * mode 0: out = float (R,C), softmax(x W^T + b) per row.  mode 1: out = long long (R,C), 1 at the row's argmax (the first index
+ * of the maximum on ties, as torch.argmax) and 0 elsewhere.  argmax (or NULL): int32 (R), written in both modes. */
+int cpc_posterior_forward(const float* x, long ldx, const float* W, const float* b, int R, int C, int mode, void* out,
+                          int* argmax, void* stream);
+
 /* ---------------------------------------------------------------- ABX evaluation ----
  * cpc/eval/ABX.py and cpc/eval/ABX/{abx_group_computation.py, dtw.pyx}: frame distances, normalised DTW and the per-group
  * score 1 - theta of get_theta_group_dtw, batched over a whole pass (csrc/abx.hip).
