@@ -127,6 +127,8 @@ SIGNATURES = {
     "cpc_phone_head_backward": (_I, [_P] * 7 + [_I, _I, _I, _P]),
     "cpc_ctc_seq_forward": (_I, [_P, _P, _P, _L, _P, _P, _P] + [_I] * 6 + [_P]),
     "cpc_ctc_seq_backward": (_I, [_P] * 4 + [_I] * 6 + [_P]),
+    "cpc_seqnorm_forward": (_I, [_P] * 5 + [_I, _I, _I, _P]),
+    "cpc_seqnorm_backward": (_I, [_P] * 6 + [_I, _I, _I, _P]),
     "cpc_probe_layout": (_I, [_I, _I, _P]),
     "cpc_probe_train_step": (_I, [_P, _L, _P, _I, _I] + [_P] * 6 + [ctypes.c_double] * 6 + [_P] * 7),
     "cpc_probe_eval": (_I, [_P, _L, _P, _I, _I] + [_P] * 7),

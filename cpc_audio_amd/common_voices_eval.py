@@ -17,9 +17,11 @@ sqrt(E[x^2] - mean^2) in float64 in loader order.
 
 The classifier's head and loss -- Conv1d (k 8, stride 4) on 256 features, log_softmax and nn.CTCLoss with the utterances'
 lengths -- run on csrc/phone_head.hip (ops.PhoneHeadCtcFunction, ops.phone_head_logits; `--hipHead` / `--no-hipHead`, see
-CTCphone_criterion).  Torch GPU ops, not the hot path: seqNorm, the optional LSTM and Dropout2d in front of the head, and the
-whole classifier for another feature width or kernel size.  CPC checkpoints load as abx.py loads them (checkpoint_args.json
-next to the checkpoint, harness.load_checkpoint); their encoder and autoregressor run on the package's HIP kernels.
+CTCphone_criterion).  What stands in front of the head -- seqNorm, the optional LSTM and the dropout -- runs on
+csrc/seqnorm.hip and csrc/lstm.hip with `--hipFront` (ops.SeqNormFunction, ops.LstmFunction: no host synchronisation, no
+per-utterance launches) and as torch GPU ops without it (the default); the whole classifier is torch ops for another feature
+width or kernel size.  CPC checkpoints load as abx.py loads them (checkpoint_args.json next to the checkpoint,
+harness.load_checkpoint); their encoder and autoregressor run on the package's HIP kernels.
 """
 import argparse
 import json
@@ -41,6 +43,7 @@ from .dataset import filterSeqs, findAllSeqs, loadFile, parseSeqLabels
 
 N_KEEP = 20           # perStep's beams
 HIP_HEAD_DEFAULT = True   # what CTCphone_criterion(hipHead=None) means where the HIP head applies
+HIP_FRONT_DEFAULT = False  # what CTCphone_criterion(hipFront=None) means: the torch front
 
 
 def load(path_item):
@@ -118,20 +121,35 @@ class CTCphone_criterion(torch.nn.Module):
     sizeKernel // 2), nn.CTCLoss(blank=nPhones, zero_infinity=True).  Same state-dict keys.  getPrediction takes the
     per-utterance feature lengths (sizeSeq // downsampling) and does not write into its input.
 
-    hipHead: the Conv1d, log_softmax and the CTC loss on csrc/phone_head.hip (seqNorm, the LSTM and the dropout stay torch ops).
-    That path takes dimEncoder 256, sizeKernel 8, CUDA fp32 features and what cpc_phone_head_layout accepts.  None: use it
-    where it applies (HIP_HEAD_DEFAULT), torch elsewhere; False: torch; True: the HIP path or NotImplementedError.  On it
-    getPrediction is not differentiable (evaluation); forward is.  last_path names the path of the last call."""
+    hipHead: the Conv1d, log_softmax and the CTC loss on csrc/phone_head.hip.  That path takes dimEncoder 256, sizeKernel 8,
+    CUDA fp32 features and what cpc_phone_head_layout accepts.  None: use it where it applies (HIP_HEAD_DEFAULT), torch
+    elsewhere; False: torch; True: the HIP path or NotImplementedError.  On it getPrediction is not differentiable
+    (evaluation); forward is.  last_path names the path of the last call.
+
+    hipFront: what stands in front of the head on HIP kernels, whichever head reads it -- seqNorm and the dropout on
+    csrc/seqnorm.hip (ops.SeqNormFunction: the utterances' lengths are read on the device, the dropout is a per-(utterance,
+    channel) factor of 0 or 2 folded into the normalisation's scale), the LSTM on csrc/lstm.hip (ops.LstmFunction on conv1's
+    parameters).  It takes dimEncoder 256 and CUDA fp32 features.  None: HIP_FRONT_DEFAULT (off); False: the torch ops; True:
+    the HIP front or NotImplementedError.  The dropout's factors come from torch's generator (bernoulli_(0.5) * 2: the
+    distribution of nn.Dropout2d on (B, 256, S), not its bits) and stay in last_channel_scale; last_front names the front of
+    the last call ("hip", "torch", None when no front op was active)."""
 
     def __init__(self, dimEncoder, nPhones, LSTM=False, sizeKernel=8, seqNorm=False, dropout=False, reduction='sum',
-                 hipHead=None):
+                 hipHead=None, hipFront=None):
         super().__init__()
         self.hipHead = hipHead
+        self.hipFront = hipFront
         self._hipConfig = dimEncoder == 256 and sizeKernel == ops.PHONE_HEAD_KERNEL
         if hipHead and not self._hipConfig:
             raise NotImplementedError("CTCphone_criterion(hipHead=True): the HIP phone head is built for dimEncoder 256 and "
                                       f"sizeKernel 8 (got {dimEncoder}, {sizeKernel})")
+        self._hipFrontConfig = dimEncoder == 256
+        if hipFront and not self._hipFrontConfig:
+            raise NotImplementedError("CTCphone_criterion(hipFront=True): the HIP seqNorm, LSTM and dropout are built for "
+                                      f"dimEncoder 256 (got {dimEncoder})")
         self.last_path = None
+        self.last_front = None
+        self.last_channel_scale = None
         self.seqNorm = seqNorm
         self.epsilon = 1e-8
         self.dropout = torch.nn.Dropout2d(p=0.5, inplace=False) if dropout else None
@@ -155,9 +173,40 @@ class CTCphone_criterion(torch.nn.Module):
                                       f"{cFeature.device}, {Lmax} target columns)")
         return ok
 
-    def _hipFeatures(self, cFeature, featureSize):
-        """What the head reads, channels-last: seqNorm, the LSTM and the dropout as getPrediction applies them."""
+    def _hipFrontPath(self, cFeature):
+        """Does this call run its seqNorm, LSTM and dropout on the HIP kernels?"""
+        if self.hipFront is False or (self.hipFront is None and not HIP_FRONT_DEFAULT) or not self._hipFrontConfig:
+            return False
+        B, S, _ = cFeature.size()
+        ok = cFeature.is_cuda and cFeature.dtype == torch.float32 and ops.seqnorm_supported(B, S) and \
+            (not self.useLSTM or ops.lstm_supported(B, S))
+        if self.hipFront and not ok:
+            raise NotImplementedError("CTCphone_criterion(hipFront=True): the HIP front takes CUDA fp32 features of a shape "
+                                      f"cpc_seqnorm_forward and cpc_lstm_layout accept (got {tuple(cFeature.size())}, "
+                                      f"{cFeature.dtype}, {cFeature.device})")
+        return ok
+
+    def _front(self, cFeature, featureSize):
+        """What the head reads, channels-last (B, S, H): seqNorm, the LSTM and the dropout.  Never writes into cFeature."""
         B, S, H = cFeature.size()
+        drop = self.dropout is not None and self.training
+        self.last_channel_scale = None
+        if not (self.seqNorm or self.useLSTM or drop):
+            self.last_front = None
+            return cFeature
+        if self._hipFrontPath(cFeature):
+            self.last_front = "hip"
+            scale = cFeature.new_empty(B, H).bernoulli_(0.5).mul_(2) if drop else None
+            self.last_channel_scale = scale
+            if self.seqNorm:                       # the dropout rides on the normalisation unless the LSTM stands between
+                cFeature = ops.SeqNormFunction.apply(cFeature, featureSize, None if self.useLSTM else scale, True)
+            if self.useLSTM:
+                cFeature = ops.LstmFunction.apply(cFeature, None, False, self.conv1.weight_ih_l0, self.conv1.weight_hh_l0,
+                                                  self.conv1.bias_ih_l0, self.conv1.bias_hh_l0)[0]
+            if drop and (self.useLSTM or not self.seqNorm):
+                cFeature = ops.SeqNormFunction.apply(cFeature, None, scale, False)
+            return cFeature
+        self.last_front = "torch"
         if self.seqNorm:
             rows = []
             for b in range(B):
@@ -173,27 +222,12 @@ class CTCphone_criterion(torch.nn.Module):
         return cFeature
 
     def getPrediction(self, cFeature, featureSize):
+        head = self.PhoneCriterionClassifier
         if self._hipPath(cFeature):
             self.last_path = "hip"
-            head = self.PhoneCriterionClassifier
-            return ops.phone_head_logits(self._hipFeatures(cFeature, featureSize), head.weight, head.bias)
+            return ops.phone_head_logits(self._front(cFeature, featureSize), head.weight, head.bias)
         self.last_path = "torch"
-        B, S, H = cFeature.size()
-        if self.seqNorm:
-            rows = []
-            for b in range(B):
-                size = int(featureSize[b])
-                m = cFeature[b, :size].mean(dim=0, keepdim=True)
-                v = cFeature[b, :size].var(dim=0, keepdim=True)
-                rows.append((cFeature[b] - m) / torch.sqrt(v + self.epsilon))
-            cFeature = torch.stack(rows)
-        if self.useLSTM:
-            cFeature = self.conv1(cFeature)[0]
-        cFeature = cFeature.permute(0, 2, 1)
-        if self.dropout is not None:
-            cFeature = self.dropout(cFeature)
-        cFeature = self.PhoneCriterionClassifier(cFeature)
-        return cFeature.permute(0, 2, 1)
+        return head(self._front(cFeature, featureSize).permute(0, 2, 1)).permute(0, 2, 1)
 
     def forward(self, cFeature, featureSize, label, labelSize):
         """featureSize: sizeSeq // downsampling per utterance (integer tensor)."""
@@ -202,7 +236,7 @@ class CTCphone_criterion(torch.nn.Module):
             self.last_path = "hip"
             head = self.PhoneCriterionClassifier
             nWindows = (cFeature.size(1) - ops.PHONE_HEAD_KERNEL) // ops.PHONE_HEAD_STRIDE + 1
-            loss = ops.PhoneHeadCtcFunction.apply(self._hipFeatures(cFeature, featureSize), head.weight, head.bias,
+            loss = ops.PhoneHeadCtcFunction.apply(self._front(cFeature, featureSize), head.weight, head.bias,
                                                   torch.clamp(featureSize // 4, max=nWindows), label, labelSize,
                                                   self.BLANK_LABEL, self.lossCriterion.reduction).view(1, -1)
             if torch.isinf(loss).sum() > 0 or torch.isnan(loss).sum() > 0:
@@ -364,6 +398,7 @@ def get_PER_args(args):
     args.in_dim = data.get("in_dim", 1)
     args.loss_reduction = data.get("loss_reduction", "mean")
     args.hipHead = data.get("hipHead", None)
+    args.hipFront = data.get("hipFront", None)
     return args
 
 
@@ -397,6 +432,10 @@ def parse_args(argv):
     t.add_argument('--hipHead', dest='hipHead', action='store_true', default=None,
                    help="The classifier's head and CTC loss on the HIP kernels (an error where they do not apply)")
     t.add_argument('--no-hipHead', dest='hipHead', action='store_false', help="The classifier's head and CTC loss as torch ops")
+    t.add_argument('--hipFront', dest='hipFront', action='store_true', default=None,
+                   help="The classifier's seqNorm, LSTM and dropout on the HIP kernels (an error where they do not apply)")
+    t.add_argument('--no-hipFront', dest='hipFront', action='store_false',
+                   help="The classifier's seqNorm, LSTM and dropout as torch ops (the default)")
     p = sub.add_parser('per')
     p.add_argument('output', type=str)
     p.add_argument('--batchSize', type=int, default=8)
@@ -478,7 +517,7 @@ def _main(args):
     feature_maker, hidden_gar, downsampling_factor = load_feature_maker(args.pathCheckpoint, args.no_pretraining, args.in_dim)
     feature_maker.cuda()
     phone_criterion = CTCphone_criterion(hidden_gar, n_phones, args.LSTM, seqNorm=args.seqNorm, dropout=args.dropout,
-                                         reduction=args.loss_reduction, hipHead=args.hipHead).cuda()
+                                         reduction=args.loss_reduction, hipHead=args.hipHead, hipFront=args.hipFront).cuda()
     print(f"Loading the validation dataset at {args.pathDB}")
     dataset_val = SingleSequenceDataset(args.pathDB, seq_val, phone_labels, inDim=args.in_dim)
     val_loader = DataLoader(dataset_val, batch_size=args.batchSize, shuffle=True)

@@ -202,6 +202,7 @@ int probe_error_flag_fetch(int clear, unsigned* out);      // probe.hip: the sam
 int abx_error_flag_fetch(int clear, unsigned* out);
 int decode_error_flag_fetch(int clear, unsigned* out);
 int phone_head_error_flag_fetch(int clear, unsigned* out); // phone_head.hip: bit 0 CPC_DEVERR_LABEL_RANGE, bit 1 CPC_DEVERR_LENGTH_RANGE
+int seqnorm_error_flag_fetch(int clear, unsigned* out);    // seqnorm.hip: CPC_DEVERR_LENGTH_RANGE
 
 static inline long align64l(long v) { return (v + 63) & ~63L; }
 

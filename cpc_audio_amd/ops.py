@@ -63,8 +63,8 @@ def check_device_errors(clear=True):
     if mask & 64:
         what.append("a PER decode or alignment received a length outside its row or a blank outside [0, P) (that score is NaN)")
     if mask & 128:
-        what.append("the phone classifier's CTC loss received an input or target length outside its range (it was clamped; that "
-                    "sequence's loss is NaN)")
+        what.append("the phone classifier's CTC loss or seqNorm received an input or target length outside its range (it was "
+                    "clamped; that sequence's loss is NaN)")
     if what:
         raise _lib.CpcHipError("device-side error: " + "; ".join(what))
 
@@ -565,6 +565,15 @@ class LstmFunction(torch.autograd.Function):
         return (dx, None, None, *grads)
 
 
+def lstm_supported(B, S, nl=1):
+    """Does cpc_lstm_layout take nl layers on (B, S, 256)?"""
+    try:
+        _layout("lstm_layout", _lib.get().cpc_lstm_layout, 3, int(B), int(S), int(nl))
+    except ValueError:
+        return False
+    return True
+
+
 CTC_MAX_SEQ = 512        # cpc_ctc_forward: longest sequence (frames) the one-workgroup recursion holds in LDS
 
 
@@ -781,6 +790,68 @@ class PhoneHeadCtcFunction(torch.autograd.Function):
             lib.check(lib.cpc_phone_head_backward(_p(x), _p(wr), _p(dlogits), _p(scratch), _p(dW), _p(db), _p(dx), B, S, C,
                                                   _stream()), "phone_head_backward")
         return dx, dW, db, None, None, None, None, None
+
+
+# ---- the PER phone classifier's front: seqNorm and dropout (csrc/seqnorm.hip) ------------------------------------------
+def seqnorm_supported(B, S):
+    """The shapes cpc_seqnorm_forward takes: B >= 1, S >= 1, B * S * 256 < 2^31."""
+    return B >= 1 and S >= 1 and B * S * _HID < (1 << 31)
+
+
+class SeqNormFunction(torch.autograd.Function):
+    """x (B, S, 256), lengths (B) int64 valid frames per utterance or None (all S), scale (B, 256) or None, normalise ->
+    y (B, S, 256): per utterance and channel, (x - mean) / sqrt(var + 1e-8) with the mean and the unbiased variance of the
+    valid frames, applied to every frame, times scale (CTCphone_criterion's seqNorm with Dropout2d's per-channel factor);
+    normalise False: x * scale.  The lengths stay on the device.  Neither lengths nor scale receives a gradient; when x does
+    not require one, no statistics are kept and backward launches nothing.  x is never written."""
+
+    @staticmethod
+    def forward(ctx, x, lengths, scale, normalise):
+        _require_cuda(x, "SeqNormFunction")
+        if x.dim() != 3 or x.shape[2] != _HID:
+            raise NotImplementedError("cpc_audio_amd.SeqNormFunction: built for (B, S, 256) features")
+        lib = _lib.get()
+        B, S, _ = x.shape
+        x = x.contiguous()
+        normalise = bool(normalise)
+        if lengths is not None:
+            lengths = _labels_on(lengths, x.device).view(-1)
+            if lengths.numel() != B:
+                raise ValueError(f"SeqNormFunction: {lengths.numel()} lengths for {B} utterances")
+        if scale is not None:
+            _require_cuda(scale, "SeqNormFunction")
+            if tuple(scale.shape) != (B, _HID):
+                raise ValueError(f"SeqNormFunction: scale of shape {tuple(scale.shape)} for {B} utterances")
+            scale = scale.detach().contiguous()
+        need_dx = ctx.needs_input_grad[0]
+        with torch.cuda.device(x.device):
+            y = torch.empty_like(x)
+            stats = torch.empty(B, 2, _HID, device=x.device, dtype=torch.float32) if need_dx and normalise else None
+            lib.check(lib.cpc_seqnorm_forward(_p(x), _p(lengths), _p(scale), _p(y), _p(stats), B, S, int(normalise), _stream()),
+                      "seqnorm_forward")
+        if need_dx:
+            ctx.save_for_backward(*(t for t in (x if normalise else None, lengths, scale, stats) if t is not None))
+            ctx.have = (normalise, lengths is not None, scale is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if dy is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        normalise, has_len, has_scale = ctx.have
+        saved = list(ctx.saved_tensors)
+        x = saved.pop(0) if normalise else None
+        lengths = saved.pop(0) if has_len else None
+        scale = saved.pop(0) if has_scale else None
+        stats = saved.pop(0) if normalise else None
+        lib = _lib.get()
+        dy = dy.contiguous()
+        B, S, _ = dy.shape
+        with torch.cuda.device(dy.device):
+            dx = torch.empty_like(dy)
+            lib.check(lib.cpc_seqnorm_backward(_p(x), _p(dy), _p(lengths), _p(scale), _p(stats), _p(dx), B, S, int(normalise),
+                                               _stream()), "seqnorm_backward")
+        return dx, None, None, None
 
 
 # ---- the frozen linear-separability step in one C call (csrc/probe.hip) ------------------------------------------------

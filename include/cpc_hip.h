@@ -69,7 +69,8 @@ int cpc_get_mfma_mode(void);
  *                                or a size outside [1, S]; it was clamped for addressing and that group's score (pair's distance) is NaN
  *   CPC_DEVERR_DECODE_RANGE      a PER entry point (cpc_ctc_beam_search, cpc_nw_align_score) met a sequence length outside
  *                                [1, T_max] (alignment: [0, L]) or a blank outside [0, P); that sequence's score is NaN
- *   CPC_DEVERR_LENGTH_RANGE      cpc_ctc_seq_forward met an input length outside [0, T] or a target length outside [0, Lmax];
+ *   CPC_DEVERR_LENGTH_RANGE      cpc_ctc_seq_forward met an input length outside [0, T] or a target length outside [0, Lmax],
+ *                                or cpc_seqnorm_forward / _backward a length outside [0, S];
  *                                it was clamped for addressing and that sequence's loss is NaN
  * The reference raises Python exceptions for such things; kernels cannot, so the wrapper (ops.check_device_errors) turns
  * the mask into a RuntimeError.  The call synchronises with the device: logging points and tests, not the step path.
@@ -383,6 +384,27 @@ int cpc_ctc_seq_forward(const float* logits, const long long* in_len, const long
                         int reduction, void* stream);
 int cpc_ctc_seq_backward(const float* logits, const float* saved, const float* dloss, float* dlogits, int B, int T, int C,
                          int Lmax, int blank, int reduction, void* stream);
+
+/* ------------------------------------------------------- PER phone classifier: seqNorm and dropout ----
+ * What CTCphone_criterion.getPrediction does in front of its head with --seqNorm and --dropout (csrc/seqnorm.hip): per
+ * utterance b and channel c, over the n = lengths[b] valid frames,
+ *   m = mean_{t<n} x[b,t,c],  v = the unbiased variance over the same frames (two-pass),  r = 1 / sqrt(v + 1e-8)
+ *   y[b,t,c] = (x[b,t,c] - m) * r * scale[b,c]   for every t < S (the padding is normalised with the valid frames' statistics)
+ * x, y, dy, dx: (B, S, 256) contiguous fp32; lengths: (B) int64 on the device, NULL = every utterance has S frames; scale:
+ * (B, 256) or NULL = 1 (nn.Dropout2d's per-(utterance, channel) factor); stats: (B, 2, 256) receives m and r for the backward,
+ * NULL when no gradient will be asked for.  normalise = 0: y = x * scale, dx = dy * scale (lengths, stats and the backward's x
+ * are not read).  B >= 1, S >= 1, B * S * 256 < 2^31 (CPC_ERR_SHAPE beyond).  y / dx must not alias an input.
+ * cpc_seqnorm_backward: g = dy * scale, xh = (x - m) * r, G1 = sum_{t<S} g, G2 = sum_{t<S} g * xh:
+ *   dx[b,t,c] = r * (g - [t < n] * (G1 / n + xh * G2 / (n - 1)))
+ * One launch per call; exact fp32, no float atomics; the summation order of one (b, c) depends on S and n only, so an utterance
+ * gives the same bits alone and inside a batch, on the 16-byte path and on the scalar path (taken when a tensor pointer is not
+ * 16-byte aligned).  A length outside [0, S] raises CPC_DEVERR_LENGTH_RANGE and is clamped; n < 2 is no error: that
+ * utterance's outputs are NaN, as torch.var's are.  Arguments are checked before any launch; nothing is allocated and
+ * nothing waits for the device. */
+int cpc_seqnorm_forward(const float* x, const long long* lengths, const float* scale, float* y, float* stats, int B, int S,
+                        int normalise, void* stream);
+int cpc_seqnorm_backward(const float* x, const float* dy, const long long* lengths, const float* scale, const float* stats,
+                         float* dx, int B, int S, int normalise, void* stream);
 
 /* ------------------------------------------------------- fused linear-probe step ----
  * The frozen step of cpc/eval/linear_separability.py (train_step :21-47 with feature_maker.optimize == False, val_step :50-68)
