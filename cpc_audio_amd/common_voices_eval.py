@@ -462,10 +462,11 @@ def load_feature_maker(path_checkpoint, no_pretraining=False, in_dim=1):
     model = train.build_model(hiddenEncoder=saved.get("hiddenEncoder", 256), hiddenGar=saved.get("hiddenGar", 256),
                               nLevelsGRU=saved.get("nLevelsGRU", 1), arMode=saved.get("arMode", "LSTM"),
                               reverse=saved.get("cpc_mode") == "reverse", sizeWindow=saved.get("sizeWindow", 20480),
-                              abspos=saved.get("abspos", False))
+                              abspos=saved.get("abspos", False), encoder_type=saved.get("encoder_type", "cpc"))
     if not no_pretraining:
         harness.load_checkpoint(str(ckpt), model)
-    return model, saved.get("hiddenGar", 256), 160
+    width = saved.get("hiddenEncoder", 256) if saved.get("arMode", "LSTM") == "no_ar" else saved.get("hiddenGar", 256)
+    return model, width, 160
 
 
 class _Tee:

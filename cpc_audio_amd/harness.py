@@ -487,7 +487,8 @@ def loadModel(pathCheckpoints):
     a ``load`` entry that points into another directory (a classifier trained on top of a CPC checkpoint), the architecture is
     read from THAT directory's checkpoint_args.json; the state dict is loaded (strict=False) from the path given.  Arguments
     missing from the file take the reference's defaults (cpc_default_config.py); the autoregressor carries its state from
-    call to call when samplingType is "sequential", as getAR builds it.  Concatenated models -- more than one checkpoint at
+    call to call when samplingType is "sequential", as getAR builds it.  ``encoder_type`` 'lfb' and ``arMode`` 'no_ar' build LFBEnconder / NoAr
+    (hiddenGar is then the encoder's width, cpc/train.py:486); 'mfcc' raises NotImplementedError.  Concatenated models -- more than one checkpoint at
     either level -- raise ValueError."""
     from .train import build_model
     if len(pathCheckpoints) != 1:
@@ -496,11 +497,11 @@ def loadModel(pathCheckpoints):
     print(f"Loading checkpoint {path}")
     saved = _architecture_args(path)
     hiddenEncoder, arMode = saved.get("hiddenEncoder", 256), saved.get("arMode", "LSTM")
-    hiddenGar = hiddenEncoder if arMode == "transformer" else saved.get("hiddenGar", 256)
+    hiddenGar = hiddenEncoder if arMode in ("transformer", "no_ar") else saved.get("hiddenGar", 256)
     model = build_model(hiddenEncoder=hiddenEncoder, hiddenGar=hiddenGar, nLevelsGRU=saved.get("nLevelsGRU", 1),
                         keepHidden=saved.get("samplingType", "samespeaker") == "sequential",
                         reverse=saved.get("cpc_mode") == "reverse", arMode=arMode, sizeWindow=saved.get("sizeWindow", 20480),
-                        abspos=saved.get("abspos", False))
+                        abspos=saved.get("abspos", False), encoder_type=saved.get("encoder_type", "cpc"))
     print(f"Loading the state dict at {path}")
     model.load_state_dict(torch.load(path, map_location="cpu")["gEncoder"], strict=False)
     return model, hiddenGar, hiddenEncoder

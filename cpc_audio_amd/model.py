@@ -9,6 +9,7 @@ forward/backward run in the HIP kernels of libcpc_hip.so.
 import torch
 import torch.nn as nn
 
+from . import ops
 from .ops import EncoderFunction, GruFunction, LstmFunction
 
 
@@ -101,6 +102,64 @@ class CPCEncoder(nn.Module):
             return x
         z = EncoderFunction.apply(x, *self._flat_params())
         return z.permute(0, 2, 1)
+
+
+class LFBEnconder(nn.Module):
+    """cpc/model.py:125-152 (--encoder_type lfb; the class name is the reference's): learned filter banks.  Conv1d(1, 2 dimEncoded,
+    400), squared modulus of adjacent channel pairs, a Hann low-pass of 400 taps at stride 160 (padding 350), log(1 + |.|) and an
+    InstanceNorm1d without affine parameters or running statistics (the same in train and eval mode).  Members and state-dict
+    keys are the reference's: ``han``, ``conv.weight`` (2 dimEncoded, 1, 400), ``conv.bias``.
+
+    Departure from the reference: its class has no ``DOWNSAMPLING`` attribute and no ``getDimOutput()``, so its own train.py and
+    FeatureModule fail on it; this one carries ``DOWNSAMPLING = 160`` (the Hann stride) and ``getDimOutput()``.
+
+    CUDA fp32 input with ``hip`` set and a shape ``ops.lfb_supported`` takes runs ops.LfbFunction (HIP: the conv output, 41 MB per
+    1.28 s window at 256 filters, is never stored; ``self.han`` is the window the kernel reads).  Unlike CPCEncoder this module
+    has a COMPLETE torch path -- the reference's formula in torch ops, any device, differentiable -- which serves every other
+    width, other dtypes and the CPU, and ``hip=False`` selects it on the GPU too."""
+
+    def __init__(self, dimEncoded, normalize=True, hip=True):
+        super().__init__()
+        self.dimEncoded = dimEncoded
+        self.conv = nn.Conv1d(1, 2 * dimEncoded, 400, stride=1)
+        self.register_buffer("han", torch.hann_window(400).view(1, 1, 400))
+        self.instancenorm = nn.InstanceNorm1d(dimEncoded, momentum=1) if normalize else None
+        self.hip = bool(hip)
+        self.DOWNSAMPLING = 160
+
+    def getDimOutput(self):
+        return self.dimEncoded
+
+    def forward(self, x):
+        """(N, 1, L) -> (N, dimEncoded, (L - 99) // 160 + 1).  On the HIP path the result is the (N, D, F) view of a contiguous
+        (N, F, D) tensor, so CPCModel's permute(0, 2, 1) yields a contiguous z."""
+        N, _, L = x.size()
+        if L < 400:
+            raise ValueError(f"LFBEnconder: a window of {L} samples is shorter than the 400 filter taps")
+        if self.hip and x.is_cuda and x.dtype == torch.float32 and self.conv.weight.dtype == torch.float32 \
+                and ops.lfb_supported(N, L, self.dimEncoded):
+            return ops.LfbFunction.apply(x, self.conv.weight, self.conv.bias, self.han, self.instancenorm is not None,
+                                         torch.is_grad_enabled())
+        x = self.conv(x).view(N, self.dimEncoded, 2, -1)
+        x = x[:, :, 0, :] ** 2 + x[:, :, 1, :] ** 2
+        x = torch.nn.functional.conv1d(x.reshape(N * self.dimEncoded, 1, -1), self.han, bias=None, stride=160, padding=350)
+        x = torch.log(1 + torch.abs(x.view(N, self.dimEncoded, -1)))
+        return x if self.instancenorm is None else self.instancenorm(x)
+
+
+class NoAr(nn.Module):
+    """cpc/model.py:207-213 (--arMode no_ar): the identity.  ``hip`` / ``reverse`` / ``keepHidden`` / ``hidden`` are there for the
+    code that reads or sets them on any autoregressor (the fused step's check, the evaluation scripts' keepHidden)."""
+
+    def __init__(self, *args):
+        super().__init__()
+        self.hip = False
+        self.reverse = False
+        self.keepHidden = False
+        self.hidden = None
+
+    def forward(self, x):
+        return x
 
 
 class CPCAR(nn.Module):

@@ -854,6 +854,84 @@ class SeqNormFunction(torch.autograd.Function):
         return dx, None, None, None
 
 
+# ---- the learned-filter-bank encoder (csrc/lfb.hip) -----------------------------------------------------------------------
+_LFB_TAPS = 400
+
+
+def lfb_frames(L):
+    """Frames of a window of L samples: the Hann low-pass has 400 taps, stride 160 and padding 350 over the L - 399 conv positions."""
+    return (L - 99) // 160 + 1
+
+
+def lfb_supported(N, L, D):
+    """The shapes cpc_lfb_energy_forward / _backward take: N >= 1, L >= 400, D a multiple of 32 up to 512, N F D < 2^31 and
+    N (L - 399) < 2^31."""
+    return (N >= 1 and L >= _LFB_TAPS and D >= 32 and D % 32 == 0 and D <= 512 and N * lfb_frames(L) * D < (1 << 31)
+            and N * (L - 399) < (1 << 31))
+
+
+class LfbFunction(torch.autograd.Function):
+    """x (N, 1, L) or (N, L), weight (2D, 1, 400), bias (2D), han (400 values), normalise, grad_enabled (the caller's
+    torch.is_grad_enabled(): inside forward grad mode is always off) -> the (N, D, F) VIEW of a contiguous
+    (N, F, D) tensor: LFBEnconder's forward (conv, squared modulus of channel pairs, Hann low-pass at stride 160, log(1 + |.|),
+    instance norm over the frames) in two launches, cpc_lfb_energy_forward and cpc_lfb_lognorm_forward.  The conv output is never
+    stored: x, the pooled energies s (N, F, D) and the norm's statistics are all that is saved, and nothing is saved when neither
+    weight nor bias requires a gradient or grad mode is off.  backward: cpc_lfb_lognorm_backward, then cpc_lfb_energy_backward,
+    which recomputes the conv; the waveform and the window receive no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, han, normalise, grad_enabled):
+        _require_cuda(x, "LfbFunction")
+        lib = _lib.get()
+        N, L = x.shape[0], x.shape[-1]
+        D = weight.shape[0] // 2
+        if x.numel() != N * L or tuple(weight.shape) != (2 * D, 1, _LFB_TAPS) or han.numel() != _LFB_TAPS:
+            raise ValueError(f"LfbFunction: x {tuple(x.shape)}, weight {tuple(weight.shape)}, han {tuple(han.shape)}")
+        if not lfb_supported(N, L, D):
+            raise NotImplementedError(f"cpc_audio_amd.LfbFunction: unsupported shape N={N} L={L} D={D} (ops.lfb_supported)")
+        x = x.detach().contiguous()
+        w, b, h = weight.detach().contiguous(), bias.detach().contiguous(), han.detach().contiguous()
+        normalise = bool(normalise)
+        need = bool(grad_enabled) and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        with torch.cuda.device(x.device):
+            F, fwd_bytes, _ = _layout("lfb_layout", lib.cpc_lfb_layout, 3, N, L, D)
+            s = torch.empty(N, F, D, device=x.device, dtype=torch.float32)
+            y = torch.empty_like(s)
+            ws = torch.empty(fwd_bytes // 4, device=x.device, dtype=torch.float32) if fwd_bytes else None
+            stats = torch.empty(N, 2, D, device=x.device, dtype=torch.float32) if need and normalise else None
+            lib.check(lib.cpc_lfb_energy_forward(_p(x), _p(w), _p(b), _p(h), _p(s), _p(ws), N, L, D, _stream()),
+                      "lfb_energy_forward")
+            lib.check(lib.cpc_lfb_lognorm_forward(_p(s), _p(y), _p(stats), N, F, D, int(normalise), _stream()),
+                      "lfb_lognorm_forward")
+        if need:
+            ctx.save_for_backward(*(t for t in (x, w, b, h, s, stats) if t is not None))    # w, b, h: the parameters' own storage
+            ctx.normalise = normalise
+        return y.permute(0, 2, 1)
+
+    @staticmethod
+    def backward(ctx, dy):
+        if dy is None or not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+            return None, None, None, None, None, None
+        saved = list(ctx.saved_tensors)
+        x, w, b, h, s = saved[:5]
+        stats = saved[5] if ctx.normalise else None
+        lib = _lib.get()
+        N, F, D = s.shape
+        L = x.shape[-1]
+        dy = dy.permute(0, 2, 1).contiguous()
+        with torch.cuda.device(dy.device):
+            bwd_bytes = _layout("lfb_layout", lib.cpc_lfb_layout, 3, N, L, D)[2]
+            ds = torch.empty_like(s)
+            dW = torch.empty(2 * D, 1, _LFB_TAPS, device=dy.device, dtype=torch.float32)
+            db = torch.empty(2 * D, device=dy.device, dtype=torch.float32)
+            ws = torch.empty(bwd_bytes // 4, device=dy.device, dtype=torch.float32)
+            lib.check(lib.cpc_lfb_lognorm_backward(_p(s), _p(stats), _p(dy), _p(ds), N, F, D, int(ctx.normalise), _stream()),
+                      "lfb_lognorm_backward")
+            lib.check(lib.cpc_lfb_energy_backward(_p(x), _p(w), _p(b), _p(h), _p(ds), _p(dW), _p(db), _p(ws), N, L, D, _stream()),
+                      "lfb_energy_backward")
+        return None, dW, db, None, None, None
+
+
 # ---- the frozen linear-separability step in one C call (csrc/probe.hip) ------------------------------------------------
 _probe_workspaces = {}
 

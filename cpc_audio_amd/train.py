@@ -7,17 +7,26 @@ import torch
 
 from .criterion import CPCUnsupersivedCriterion
 from .dist import FlatGradAllReduce
-from .model import CPCAR, CPCEncoder, CPCModel
+from .model import CPCAR, CPCEncoder, CPCModel, LFBEnconder, NoAr
 from .optim import Adam
 
 
 def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False, reverse=False, arMode="GRU",
-                sizeWindow=20480, abspos=False, transformerDropout=0.1, lstmKernel=False):
+                sizeWindow=20480, abspos=False, transformerDropout=0.1, lstmKernel=False, encoder_type="cpc"):
     """cpc/feature_loader.py:124-153 (getEncoder / getAR) + cpc/train.py:311.  arMode 'GRU' (north star) or
     'transformer' (BASELINE.json config 4: buildTransformerAR(hiddenEncoder, 1, sizeWindow // 160, abspos)); 'LSTM' /
-    'RNN' as the reference (lstmKernel: the LSTM on the HIP kernels, CPCAR)."""
-    enc = CPCEncoder(hiddenEncoder, "layerNorm")
-    if arMode == "transformer":
+    'RNN' as the reference (lstmKernel: the LSTM on the HIP kernels, CPCAR); 'no_ar': the identity, and the context width is
+    the encoder's (cpc/train.py:486).  encoder_type 'cpc' or 'lfb' (learned filter banks, LFBEnconder); 'mfcc' needs
+    torchaudio and is not built here."""
+    if encoder_type == "mfcc":
+        raise NotImplementedError("encoder_type 'mfcc' is torchaudio.transforms.MFCC in the reference; torchaudio is not a "
+                                  "dependency of this package and no MFCC encoder is built here")
+    if encoder_type not in ("cpc", "lfb"):
+        raise ValueError(f"encoder_type must be 'cpc', 'lfb' or 'mfcc', got {encoder_type!r}")
+    enc = LFBEnconder(hiddenEncoder) if encoder_type == "lfb" else CPCEncoder(hiddenEncoder, "layerNorm")
+    if arMode == "no_ar":
+        ar = NoAr()
+    elif arMode == "transformer":
         from .transformers import buildTransformerAR
         ar = buildTransformerAR(hiddenEncoder, 1, sizeWindow // 160, abspos, dropout=transformerDropout)
     else:

@@ -406,6 +406,34 @@ int cpc_seqnorm_forward(const float* x, const long long* lengths, const float* s
 int cpc_seqnorm_backward(const float* x, const float* dy, const long long* lengths, const float* scale, const float* stats,
                          float* dx, int B, int S, int normalise, void* stream);
 
+/* ------------------------------------------------------- learned-filter-bank encoder (LFBEnconder) ----
+ * cpc/model.py:125-152 (csrc/lfb.hip).  x (N, L) mono waveform, W (2D, 400), b (2D), han (400), all fp32 and read only:
+ *   y[n,c,t] = b[c] + sum_j W[c,j] x[n,t+j]                  t = 0 .. L-400 (never stored)
+ *   e[n,d,t] = y[n,2d,t]^2 + y[n,2d+1,t]^2
+ *   s[n,f,d] = sum_{j<400} han[j] e[n,d,160f-350+j]           positions outside [0, L-400] count as zero, F = (L-99)/160 + 1
+ * cpc_lfb_energy_forward writes s channels-last (N, F, D) in one launch: the conv is a Toeplitz GEMM on exact-f32 MFMAs whose
+ * epilogue squares, pairs and Hann-pools in registers.  cpc_lfb_energy_backward takes gs (N, F, D) and OVERWRITES dW (2D, 400)
+ * and db (2D): it recomputes y tile by tile, forms gy = 2 y ge with ge[d,t] = sum_f han[t-160f+350] gs[n,f,d] (at most three
+ * terms) and feeds it straight into dW[c,j] = sum_{n,t} gy[n,c,t] x[n,t+j], db[c] = sum gy; per-workgroup partial tiles in
+ * ws are summed by one reduce kernel in a fixed order (no float atomics): every result is bit-reproducible.
+ * cpc_lfb_layout: sizes[0] = F, sizes[1] / sizes[2] = bytes of ws for the forward (0: ws may be NULL) / the backward; neither
+ * grows with N * D * (L - 399).
+ * cpc_lfb_lognorm_forward: u = log(1 + |s|); normalise: y = (u - m) / sqrt(v + 1e-5) with m, v the mean and the biased variance
+ * (two-pass) of u over the F frames of each (n, d) (nn.InstanceNorm1d without affine parameters or running statistics);
+ * stats (N, 2, D) receives m and 1 / sqrt(v + 1e-5), NULL when no gradient will be asked for.  normalise = 0: y = u.
+ * cpc_lfb_lognorm_backward: ds from dy, s and stats (not read when normalise = 0).  One launch each; y / ds must not alias an
+ * input.
+ * CPC_ERR_SHAPE for N < 1, L < 400 (F < 2 for the lognorm calls), D % 32 != 0, D > 512, N * F * D >= 2^31 or
+ * N * (L - 399) >= 2^31.  Arguments are checked before any launch; nothing is allocated, copied to the host or waited for. */
+int cpc_lfb_layout(int N, int L, int D, long* sizes);
+int cpc_lfb_energy_forward(const float* x, const float* W, const float* b, const float* han, float* s, void* ws, int N, int L,
+                           int D, void* stream);
+int cpc_lfb_energy_backward(const float* x, const float* W, const float* b, const float* han, const float* gs, float* dW,
+                            float* db, void* ws, int N, int L, int D, void* stream);
+int cpc_lfb_lognorm_forward(const float* s, float* y, float* stats, int N, int F, int D, int normalise, void* stream);
+int cpc_lfb_lognorm_backward(const float* s, const float* stats, const float* dy, float* ds, int N, int F, int D, int normalise,
+                             void* stream);
+
 /* ------------------------------------------------------- fused linear-probe step ----
  * The frozen step of cpc/eval/linear_separability.py (train_step :21-47 with feature_maker.optimize == False, val_step :50-68)
  * for SpeakerCriterion / PhoneCriterion: logits = x W^T + b on R rows of 256 features, the mean cross-entropy, the accuracy
