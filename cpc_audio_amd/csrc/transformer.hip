@@ -143,7 +143,9 @@ __global__ __launch_bounds__(kAmaxSlots) void bounds_begin_kernel(float* __restr
 // counter-based generator torch uses on GPUs -- so the backward regenerates it instead of reading a saved mask, and a test
 // can ask for exactly the mask a layer call used (cpc_dropout_keep_mask).
 //   site 0: attention probability (b*8 + head, i, j) at flat index ((b*8 + head)*S + i)*S + j
-//   site 1: hidden activation (row, col): block (row >> 2)*2048 + col, word row & 3 (philox.h)
+//   site 1: hidden activation (row, col): block (row >> 2)*1024 + (((col >> 6) << 5) | (col & 31)), word row & 3, the word's high
+//           16 bits if col & 32 else its low 16 (philox.h)
+// Both numberings are pinned bit for bit by an independent reference (tests/philox_util.py).
 // Site 0 (attention probabilities): the four words of one Philox block belong to the four rows 4u .. 4u+3 of one column --
 // block index ((b*8 + head) * ceil(S/4) + (i >> 2)) * S + j, word i & 3 -- because that is what one lane of an MFMA
 // accumulator holds (c_row: registers 4m .. 4m+3 are four consecutive rows of one column): a lane draws 16 blocks for its 64

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import philox_util as PU
 from emu_util import P, emu, rel_err
 from oracle import transformer_oracle as T
 
@@ -207,9 +208,13 @@ def test_transformer_layer_training_dropout_emulated(B, S, abspos, p_drop, gemm_
     for m in (attn_keep, ffn_keep):
         assert set(m.unique().tolist()) <= {0.0, float(np.float32(1.0) / (np.float32(1.0) - np.float32(p_drop)))}
         assert abs((m > 0).float().mean().item() - (1 - p_drop)) < 0.01
+    # ... and they are the masks of the independent reference (tests/philox_util.py), bit for bit -- which the oracle runs on:
+    # the kernels apply what the specification says, not merely what the mask kernel reports
+    ref_attn, ref_ffn = PU.attn_keep_ref(B * 8, S, p_drop, seed), PU.ffn_keep_ref(B * S, p_drop, seed).view(B, S, 2048)
+    assert torch.equal(attn_keep, ref_attn) and torch.equal(ffn_keep, ref_ffn)
     leaves = {k: v.clone().requires_grad_(True) for k, v in prm.items()}
     xr = x.clone().requires_grad_(True)
-    yr = T.layer_forward(leaves, xr, attn_keep=attn_keep, ffn_keep=ffn_keep)
+    yr = T.layer_forward(leaves, xr, attn_keep=ref_attn, ffn_keep=ref_ffn)
     (yr * dy).sum().backward()
     assert (out - yr).abs().max().item() < 1e-5
     assert rel_err(dx, xr.grad) < 1e-5

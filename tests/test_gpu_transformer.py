@@ -170,6 +170,10 @@ def test_transformer_layer_trains_with_the_references_dropout():
     lib.check(lib.cpc_dropout_keep_mask(P(ffn_keep), ffn_keep.numel(), 1, S, p_drop, seed, st), "keep_mask")
     torch.cuda.synchronize()
     assert abs((ffn_keep > 0).float().mean().item() - 0.9) < 2e-3 and abs((attn_keep > 0).float().mean().item() - 0.9) < 5e-3
+    # the masks the library reports are those of the independent reference (tests/philox_util.py), bit for bit
+    import philox_util as PU
+    assert torch.equal(attn_keep.cpu(), PU.attn_keep_ref(B * 8, S, p_drop, seed))
+    assert torch.equal(ffn_keep.cpu(), PU.ffn_keep_ref(B * S, p_drop, seed).view(B, S, 2048))
     leaves = {k: v.clone().requires_grad_(True) for k, v in prm.items()}
     xr = x.clone().requires_grad_(True)
     yr = T.layer_forward(leaves, xr, prefix="0.", attn_keep=attn_keep.cpu(), ffn_keep=ffn_keep.cpu())
