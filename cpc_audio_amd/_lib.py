@@ -134,6 +134,9 @@ SIGNATURES = {
     "cpc_lfb_energy_backward": (_I, [_P] * 8 + [_I, _I, _I, _P]),
     "cpc_lfb_lognorm_forward": (_I, [_P] * 3 + [_I, _I, _I, _I, _P]),
     "cpc_lfb_lognorm_backward": (_I, [_P] * 4 + [_I, _I, _I, _I, _P]),
+    "cpc_pred_conv_layout": (_I, [_I, _I, _I, _I, _P]),
+    "cpc_pred_conv_forward": (_I, [_P] * 5 + [_I] * 5 + [_F, _I, _P]),
+    "cpc_pred_conv_backward": (_I, [_P] * 8 + [_I] * 5 + [_F, _I, _P]),
     "cpc_probe_layout": (_I, [_I, _I, _P]),
     "cpc_probe_train_step": (_I, [_P, _L, _P, _I, _I] + [_P] * 6 + [ctypes.c_double] * 6 + [_P] * 7),
     "cpc_probe_eval": (_I, [_P, _L, _P, _I, _I] + [_P] * 7),

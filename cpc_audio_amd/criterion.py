@@ -121,6 +121,9 @@ _TORCH_PREDICTORS = {
     "conv8": lambda a, e: ShiftedConv(a, e, 8),
     "conv12": lambda a, e: ShiftedConv(a, e, 12),
 }
+# ... of which these are plain feed-forward arithmetic and run, with ``hipPredictors``, as grouped causal convolutions on
+# csrc/pred_conv.hip (ops.PredConvFunction) where every predictor is of the class named here
+_HIP_PREDICTORS = {"ffd": FFNetwork, "conv4": ShiftedConv, "conv8": ShiftedConv, "conv12": ShiftedConv}
 
 
 class PredictionNetwork(nn.Module):
@@ -133,8 +136,12 @@ class PredictionNetwork(nn.Module):
     reference's parameter names whose predictions the HIP score kernels take as a tensor (``scores_apart``)."""
 
     def __init__(self, nPredicts, dimOutputAR, dimOutputEncoder, rnnMode=None, dropout=False,
-                 sizeInputSeq=116, transformerDropout=0.1):
+                 sizeInputSeq=116, transformerDropout=0.1, hipPredictors=False):
         super().__init__()
+        # hipPredictors (an addition; off by default): ``ffd`` and ``conv4/8/12`` predictors run on csrc/pred_conv.hip where
+        # _hip_predictors_apply allows, on the torch modules otherwise; last_path names what the last call took
+        self.hipPredictors = bool(hipPredictors)
+        self.last_path = None
         if dimOutputAR != 256 or dimOutputEncoder != 256:
             raise NotImplementedError("the HIP criterion is built for hiddenGar == hiddenEncoder == 256")
         # (any number of prediction steps: the score tiles hold 16 heads per wavefront, a larger criterion is walked in groups of
@@ -194,8 +201,56 @@ class PredictionNetwork(nn.Module):
             return TransformerGroupFunction.apply(c, p, seed, len(layers), *kinds)
         if all(isinstance(p, nn.Linear) and p.bias is None for p in self.predictors):
             return torch.nn.functional.linear(c, self.stacked_weight())
+        if self._hip_predictors_apply(c):
+            self.last_path = "hip"
+            return self._hip_predictions(c)
+        self.last_path = "torch"
         out = [p(c) for p in self.predictors]
         return torch.cat([o[0] if isinstance(o, tuple) else o for o in out], dim=2)     # (recurrent cells return (y, state))
+
+    def _hip_predictors_apply(self, c):
+        """hipPredictors: do the K predictors run on csrc/pred_conv.hip for this input?  Only this package's own ShiftedConv /
+        FFNetwork (without dropout) on CUDA fp32 input of a shape the kernels take; anything else stays on the torch modules."""
+        if not self.hipPredictors or self.rnnMode not in _HIP_PREDICTORS or len(self.predictors) == 0:
+            return False
+        if not c.is_cuda or c.dtype != torch.float32 or c.dim() != 3 or c.shape[2] != 256:
+            return False
+        kind = _HIP_PREDICTORS[self.rnnMode]
+        if not all(type(p) is kind for p in self.predictors):
+            return False
+        if kind is FFNetwork:
+            if any(p.drop.p != 0 or not isinstance(p.lin1.module, nn.Linear) or not isinstance(p.lin2.module, nn.Linear)
+                   or tuple(q.module.weight.shape) != (256, 256) or q.module.bias is None
+                   for p in self.predictors for q in (p.lin1, p.lin2)):
+                return False
+            ks = 1
+        else:
+            ks = self.predictors[0].kernelSize
+            if any(p.kernelSize != ks or not isinstance(p.module.module, nn.Conv1d) or p.module.module.bias is None
+                   or tuple(p.module.module.weight.shape) != (256, 256, ks) for p in self.predictors):
+                return False
+        from .ops import pred_conv_supported
+        return pred_conv_supported(c.shape[0], c.shape[1], len(self.predictors), ks)
+
+    def _hip_predictions(self, c):
+        """The K ShiftedConv / FFNetwork predictors as grouped causal convolutions (ops.PredConvFunction) on the heads' stacked
+        parameters: one call for conv4 / conv8 / conv12, two for ffd (lin1 with its ReLU on the shared input, lin2 per head)."""
+        from .ops import PredConvFunction
+        K = len(self.predictors)
+
+        def stacked(key, layers):
+            ks = layers[0].module.weight[0, 0].numel()
+            w = stacked_parameters(self, key + ".weight", [l.module.weight for l in layers], (K, 256, 256, ks))
+            b = stacked_parameters(self, key + ".bias", [l.module.bias for l in layers])
+            return w, b, layers[0].weight
+
+        if self.rnnMode == "ffd":
+            w1, b1, s1 = stacked("lin1", [p.lin1 for p in self.predictors])
+            w2, b2, s2 = stacked("lin2", [p.lin2 for p in self.predictors])
+            h = PredConvFunction.apply(c, w1, b1, s1, True, True)
+            return PredConvFunction.apply(h, w2, b2, s2, False, False)
+        w, b, s = stacked("conv", [p.module for p in self.predictors])
+        return PredConvFunction.apply(c, w, b, s, False, True)
 
     def stacked_weight(self):
         """(K*256, 256): the K head weights stacked along the output dimension (stacked_parameters: no per-step cat)."""
@@ -242,7 +297,8 @@ class CPCUnsupersivedCriterion(BaseCriterion):
                  speakerEmbedding=0,
                  nSpeakers=0,
                  sizeInputSeq=128,
-                 transformerDropout=0.1):
+                 transformerDropout=0.1,
+                 hipPredictors=False):  # ffd / conv4 / conv8 / conv12 predictors on csrc/pred_conv.hip (PredictionNetwork)
         super().__init__()
         if speakerEmbedding > 0:
             raise NotImplementedError("speakerEmbedding is deprecated in the reference "
@@ -250,7 +306,7 @@ class CPCUnsupersivedCriterion(BaseCriterion):
         self.speakerEmb = None
         self.wPrediction = PredictionNetwork(nPredicts, dimOutputAR, dimOutputEncoder, rnnMode=rnnMode,
                                              dropout=dropout, sizeInputSeq=sizeInputSeq - nPredicts,
-                                             transformerDropout=transformerDropout)
+                                             transformerDropout=transformerDropout, hipPredictors=hipPredictors)
         self.nPredicts = nPredicts
         self.negativeSamplingExt = negativeSamplingExt
         # (any number: the kernels walk candidates in 16-wide tiles and mask the padding of the last one, ops.prepare_negatives)

@@ -792,6 +792,71 @@ class PhoneHeadCtcFunction(torch.autograd.Function):
         return dx, dW, db, None, None, None, None, None
 
 
+# ---- the feed-forward prediction networks: ffd, conv4 / conv8 / conv12 (csrc/pred_conv.hip) ------------------------------
+def pred_conv_layout(B, W, G, ks):
+    """(wr floats, backward scratch floats, y floats) of cpc_pred_conv_layout; ValueError for a shape the kernels do not take."""
+    return _layout("pred_conv_layout", _lib.get().cpc_pred_conv_layout, 3, int(B), int(W), int(G), int(ks))
+
+
+def pred_conv_supported(B, W, G, ks):
+    """The shapes cpc_pred_conv_forward / _backward take: 1 <= G <= 64 heads, 1 <= ks <= 16 taps, B, W >= 1 and
+    B W G 256 < 2^31."""
+    try:
+        pred_conv_layout(B, W, G, ks)
+    except ValueError:
+        return False
+    return True
+
+
+class PredConvFunction(torch.autograd.Function):
+    """x (B, W, 256) read by every head, or (B, W, G*256) with head g at columns g*256.. (``shared`` False); weight
+    (G, 256, 256, ks): the heads' Conv1d weights stacked (an nn.Linear weight is ks = 1); bias (G, 256); scale: the equalized
+    layer's constant; relu -> (B, W, G*256), head g at columns g*256..:
+    act(scale * (bias_g + causal conv of x_g with weight_g over the time axis)), frames in front of a window read as zero
+    (cpc_pred_conv_forward / _backward).  Saves x, and y when relu is set."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, scale, relu, shared):
+        _require_cuda(x, "PredConvFunction")
+        lib = _lib.get()
+        if weight.dim() != 4 or tuple(weight.shape[1:3]) != (_HID, _HID) or tuple(bias.shape) != (weight.shape[0], _HID):
+            raise NotImplementedError("cpc_audio_amd.PredConvFunction: a (G, 256, 256, ks) weight and a (G, 256) bias expected")
+        G, ks = weight.shape[0], weight.shape[3]
+        if x.dim() != 3 or x.shape[2] != (_HID if shared else G * _HID):
+            raise NotImplementedError(f"cpc_audio_amd.PredConvFunction: x of shape {tuple(x.shape)} for {G} heads "
+                                      f"({'shared' if shared else 'per-head'} input)")
+        B, W, _ = x.shape
+        x = x.contiguous()
+        weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
+        with torch.cuda.device(x.device):
+            sizes = pred_conv_layout(B, W, G, ks)
+            wr = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
+            y = torch.empty(B, W, G * _HID, device=x.device, dtype=torch.float32)
+            lib.check(lib.cpc_pred_conv_forward(_p(x), _p(weight), _p(bias), _p(wr), _p(y), B, W, G, ks, int(bool(shared)),
+                                                float(scale), int(bool(relu)), _stream()), "pred_conv_forward")
+        ctx.save_for_backward(x, weight, *((y,) if relu else ()))
+        ctx.dims = (B, W, G, ks, bool(shared), float(scale), bool(relu), sizes[1])
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors[:2]
+        B, W, G, ks, shared, scale, relu, nscr = ctx.dims
+        if dy is None:
+            return (None,) * 6
+        y = ctx.saved_tensors[2] if relu else None
+        lib = _lib.get()
+        with torch.cuda.device(x.device):
+            scratch = torch.empty(nscr, device=x.device, dtype=torch.float32)
+            dw = torch.empty_like(weight)
+            db = torch.empty(G, _HID, device=x.device, dtype=torch.float32)
+            dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+            lib.check(lib.cpc_pred_conv_backward(_p(x), _p(weight), _p(y), _p(dy.contiguous()), _p(scratch), _p(dw), _p(db),
+                                                 _p(dx), B, W, G, ks, int(shared), scale, int(relu), _stream()),
+                      "pred_conv_backward")
+        return dx, dw, db, None, None, None
+
+
 # ---- the PER phone classifier's front: seqNorm and dropout (csrc/seqnorm.hip) ------------------------------------------
 def seqnorm_supported(B, S):
     """The shapes cpc_seqnorm_forward takes: B >= 1, S >= 1, B * S * 256 < 2^31."""

@@ -35,10 +35,11 @@ def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False
 
 
 def build_criterion(nPredicts=12, hiddenGar=256, hiddenEncoder=256, negativeSamplingExt=128,
-                    sizeWindow=20480, downsampling=160, mode=None, rnnMode="linear", transformerDropout=0.1, dropout=False):
+                    sizeWindow=20480, downsampling=160, mode=None, rnnMode="linear", transformerDropout=0.1, dropout=False,
+                    hipPredictors=False):
     return CPCUnsupersivedCriterion(nPredicts, hiddenGar, hiddenEncoder, negativeSamplingExt, mode=mode,
                                     rnnMode=rnnMode, dropout=dropout, sizeInputSeq=sizeWindow // downsampling,
-                                    transformerDropout=transformerDropout)
+                                    transformerDropout=transformerDropout, hipPredictors=hipPredictors)
 
 
 def load_flat_params(model, criterion, params):

@@ -436,6 +436,32 @@ int cpc_lfb_lognorm_forward(const float* s, float* y, float* stats, int N, int F
 int cpc_lfb_lognorm_backward(const float* s, const float* stats, const float* dy, float* ds, int N, int F, int D, int normalise,
                              void* stream);
 
+/* ------------------------------------------------------- feed-forward prediction networks ----
+ * --rnnMode ffd / conv4 / conv8 / conv12 of cpc/criterion/criterion.py:11-41,69-81 on the equalized layers of
+ * custom_layers.py (csrc/pred_conv.hip): G heads of a causal convolution over the time axis, 256 -> 256 channels, ks taps,
+ *   y[b, t, g * 256 + o] = act( scale * ( bias[g][o] + sum_{j<ks} sum_{i<256} x_g[b, t - (ks-1) + j, i] * w[g][o][i][j] ) )
+ * with frames t' < 0 read as zero, act = ReLU when relu != 0 and the identity otherwise.  scale is the equalized layer's
+ * constant sqrt(2 / (256 * ks)), which multiplies the wrapped module's output, bias included.  ShiftedConv is one call
+ * (shared = 1, relu = 0); FFNetwork is two with ks = 1: lin1 (shared = 1, relu = 1), then lin2 on lin1's output (shared = 0).
+ * x: (B, W, 256), read by every head (shared != 0), or (B, W, G * 256) with head g at columns g * 256 (shared = 0).
+ * w (G, 256, 256, ks) and dw: the heads' Conv1d weights one behind the other in torch's layout; bias and db (G, 256);
+ * y and dy (B, W, G * 256): the layout cpc_nce_scores_forward reads.  fp32 storage; products at the library's fp32 level, as
+ * cpc_gemm_nt's (three bf16 pieces per operand by default, exact-f32 MFMA after cpc_set_mfma_mode(0)); no float atomics
+ * and fixed summation orders: identical calls give identical bits, and a batch item's results do not depend on the batch
+ * around it.  Arguments are checked before any launch; nothing is allocated and nothing waits for the device.
+ * cpc_pred_conv_layout(B, W, G, ks, sizes): 1 <= G <= 64, 1 <= ks <= 16, B, W >= 1, B * W * G * 256 < 2^31 (CPC_ERR_SHAPE
+ *   beyond).  sizes[0] = floats of wr (G * ks * 65536), sizes[1] = scratch floats of the backward, sizes[2] = floats of y.
+ * cpc_pred_conv_forward: wr receives the weight K-major over a window's floats, wr[g][o][j * 256 + i] (one launch).
+ * cpc_pred_conv_backward: dy -> dw, db OVERWRITTEN (row slabs summed in slab order) and, when dx is non-NULL, dx of x's shape:
+ *   with a shared input the sum over heads and taps runs inside the call in a fixed order (one accumulator per output, or
+ *   up to 8 groups of consecutive heads whose partial sums are added in group order).
+ *   relu != 0 masks dy where y <= 0 first (y: the forward's output; not read otherwise and may be NULL). */
+int cpc_pred_conv_layout(int B, int W, int G, int ks, long* sizes);
+int cpc_pred_conv_forward(const float* x, const float* w, const float* bias, float* wr, float* y, int B, int W, int G, int ks,
+                          int shared, float scale, int relu, void* stream);
+int cpc_pred_conv_backward(const float* x, const float* w, const float* y, const float* dy, float* scratch, float* dw, float* db,
+                           float* dx, int B, int W, int G, int ks, int shared, float scale, int relu, void* stream);
+
 /* ------------------------------------------------------- fused linear-probe step ----
  * The frozen step of cpc/eval/linear_separability.py (train_step :21-47 with feature_maker.optimize == False, val_step :50-68)
  * for SpeakerCriterion / PhoneCriterion: logits = x W^T + b on R rows of 256 features, the mean cross-entropy, the accuracy
