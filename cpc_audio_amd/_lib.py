@@ -117,6 +117,12 @@ SIGNATURES = {
     "cpc_lstm_layout": (_I, [_I, _I, _I, _P]),
     "cpc_lstm_forward": (_I, [_P] * 9 + [_I, _I, _I, _I, _P]),
     "cpc_lstm_backward": (_I, [_P] * 10 + [_I, _I, _I, _I, _P]),
+    "cpc_lstm_group_layout": (_I, [_I, _I, _I, _P]),
+    "cpc_lstm_group_forward": (_I, [_P] * 8 + [_I, _I, _I, _I, _P]),
+    "cpc_lstm_group_backward": (_I, [_P] * 12 + [_I, _I, _I, _I, _P]),
+    "cpc_rnn_layout": (_I, [_I, _I, _I, _I, _P]),
+    "cpc_rnn_forward": (_I, [_P] * 7 + [_I, _I, _I, _I, _I, _P]),
+    "cpc_rnn_backward": (_I, [_P] * 9 + [_I, _I, _I, _I, _I, _P]),
     "cpc_supervised_layout": (_I, [_I, _I, _I, _I, _P]),
     "cpc_classifier_forward": (_I, [_P, _L] + [_P] * 6 + [_I, _I, _P]),
     "cpc_classifier_backward": (_I, [_P, _L] + [_P] * 9 + [_I, _I, _P]),

@@ -121,9 +121,12 @@ _TORCH_PREDICTORS = {
     "conv8": lambda a, e: ShiftedConv(a, e, 8),
     "conv12": lambda a, e: ShiftedConv(a, e, 12),
 }
-# ... of which these are plain feed-forward arithmetic and run, with ``hipPredictors``, as grouped causal convolutions on
-# csrc/pred_conv.hip (ops.PredConvFunction) where every predictor is of the class named here
-_HIP_PREDICTORS = {"ffd": FFNetwork, "conv4": ShiftedConv, "conv8": ShiftedConv, "conv12": ShiftedConv}
+# ... which run, with ``hipPredictors``, on HIP kernels where every predictor is of the class named here: the feed-forward ones as
+# grouped causal convolutions on csrc/pred_conv.hip (ops.PredConvFunction), the recurrent ones as K recurrences side by side on
+# csrc/lstm.hip (ops.LstmGroupFunction) and csrc/rnn.hip (ops.RnnFunction)
+_HIP_PREDICTORS = {"ffd": FFNetwork, "conv4": ShiftedConv, "conv8": ShiftedConv, "conv12": ShiftedConv,
+                   "LSTM": nn.LSTM, "RNN": nn.RNN}
+_CELL_PARAMS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
 
 
 class PredictionNetwork(nn.Module):
@@ -133,13 +136,15 @@ class PredictionNetwork(nn.Module):
     ``buildTransformerAR(dimOutputEncoder, 1, sizeInputSeq, False)`` on the HIP transformer layer
     (``transformerDropout`` is an addition -- the reference's layers always use 0.1, which has no parity).  The reference's
     other choices (:63-81: ``RNN``, ``LSTM``, ``ffd``, ``conv4/8/12``; none in a BASELINE config) are torch modules with the
-    reference's parameter names whose predictions the HIP score kernels take as a tensor (``scores_apart``)."""
+    reference's parameter names whose predictions the HIP score kernels take as a tensor (``scores_apart``); with
+    ``hipPredictors`` those predictions come from HIP kernels on the modules' parameters (``_hip_predictions``)."""
 
     def __init__(self, nPredicts, dimOutputAR, dimOutputEncoder, rnnMode=None, dropout=False,
                  sizeInputSeq=116, transformerDropout=0.1, hipPredictors=False):
         super().__init__()
-        # hipPredictors (an addition; off by default): ``ffd`` and ``conv4/8/12`` predictors run on csrc/pred_conv.hip where
-        # _hip_predictors_apply allows, on the torch modules otherwise; last_path names what the last call took
+        # hipPredictors (an addition; off by default): ``ffd`` and ``conv4/8/12`` predictors run on csrc/pred_conv.hip, ``LSTM`` and
+        # ``RNN`` predictors on csrc/lstm.hip / csrc/rnn.hip where _hip_predictors_apply allows, on the torch modules otherwise;
+        # last_path names what the last call took
         self.hipPredictors = bool(hipPredictors)
         self.last_path = None
         if dimOutputAR != 256 or dimOutputEncoder != 256:
@@ -209,8 +214,9 @@ class PredictionNetwork(nn.Module):
         return torch.cat([o[0] if isinstance(o, tuple) else o for o in out], dim=2)     # (recurrent cells return (y, state))
 
     def _hip_predictors_apply(self, c):
-        """hipPredictors: do the K predictors run on csrc/pred_conv.hip for this input?  Only this package's own ShiftedConv /
-        FFNetwork (without dropout) on CUDA fp32 input of a shape the kernels take; anything else stays on the torch modules."""
+        """hipPredictors: do the K predictors run on the HIP kernels for this input?  Only this package's own ShiftedConv /
+        FFNetwork (without dropout), or plain one-layer nn.LSTM / tanh nn.RNN cells of 256 -> 256 as the reference builds them, on
+        CUDA fp32 input of a shape the kernels take; anything else stays on the torch modules."""
         if not self.hipPredictors or self.rnnMode not in _HIP_PREDICTORS or len(self.predictors) == 0:
             return False
         if not c.is_cuda or c.dtype != torch.float32 or c.dim() != 3 or c.shape[2] != 256:
@@ -218,6 +224,20 @@ class PredictionNetwork(nn.Module):
         kind = _HIP_PREDICTORS[self.rnnMode]
         if not all(type(p) is kind for p in self.predictors):
             return False
+        if kind in (nn.LSTM, nn.RNN):
+            K, (B, W, _) = len(self.predictors), c.shape
+            for p in self.predictors:
+                if (p.num_layers != 1 or p.input_size != 256 or p.hidden_size != 256 or not p.bias or p.bidirectional
+                        or p.dropout != 0):
+                    return False
+                if kind is nn.LSTM and (p.proj_size != 0 or not p.batch_first):
+                    return False
+                if kind is nn.RNN and (p.nonlinearity != "tanh" or p.batch_first):
+                    return False
+                if any(getattr(p, n).dtype != torch.float32 or not getattr(p, n).is_cuda for n in _CELL_PARAMS):
+                    return False
+            from .ops import lstm_group_supported, rnn_supported
+            return lstm_group_supported(B, W, K) if kind is nn.LSTM else rnn_supported(B, W, K, 1)
         if kind is FFNetwork:
             if any(p.drop.p != 0 or not isinstance(p.lin1.module, nn.Linear) or not isinstance(p.lin2.module, nn.Linear)
                    or tuple(q.module.weight.shape) != (256, 256) or q.module.bias is None
@@ -234,9 +254,20 @@ class PredictionNetwork(nn.Module):
 
     def _hip_predictions(self, c):
         """The K ShiftedConv / FFNetwork predictors as grouped causal convolutions (ops.PredConvFunction) on the heads' stacked
-        parameters: one call for conv4 / conv8 / conv12, two for ffd (lin1 with its ReLU on the shared input, lin2 per head)."""
-        from .ops import PredConvFunction
+        parameters: one call for conv4 / conv8 / conv12, two for ffd (lin1 with its ReLU on the shared input, lin2 per head).
+        The K nn.LSTM / nn.RNN predictors as K recurrences side by side (ops.LstmGroupFunction / ops.RnnFunction): one call."""
+        from .ops import LstmGroupFunction, PredConvFunction, RnnFunction
         K = len(self.predictors)
+        if self.rnnMode in ("LSTM", "RNN"):
+            # the K cells' parameters, kind by kind, as views of one buffer each; the modules keep them under the reference's keys.
+            # nn.RNN without batch_first (criterion.py:62-64) walks the batch axis of c: T = B, R = W, time-major
+            n = self.predictors[0].weight_hh_l0.shape[0]
+            shapes = ((K * n, 256), (K, n, 256), (K * n,), (K * n,))
+            kinds = [stacked_parameters(self, name, [getattr(p, name) for p in self.predictors], shape)
+                     for name, shape in zip(_CELL_PARAMS, shapes)]
+            if self.rnnMode == "LSTM":
+                return LstmGroupFunction.apply(c, False, *kinds)
+            return RnnFunction.apply(c, None, True, False, *kinds)[0]
 
         def stacked(key, layers):
             ks = layers[0].module.weight[0, 0].numel()
@@ -298,7 +329,7 @@ class CPCUnsupersivedCriterion(BaseCriterion):
                  nSpeakers=0,
                  sizeInputSeq=128,
                  transformerDropout=0.1,
-                 hipPredictors=False):  # ffd / conv4 / conv8 / conv12 predictors on csrc/pred_conv.hip (PredictionNetwork)
+                 hipPredictors=False):  # ffd / conv4 / conv8 / conv12 / LSTM / RNN predictors on HIP kernels (PredictionNetwork)
         super().__init__()
         if speakerEmbedding > 0:
             raise NotImplementedError("speakerEmbedding is deprecated in the reference "

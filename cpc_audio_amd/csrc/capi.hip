@@ -113,15 +113,16 @@ extern "C" int cpc_streams_overlap(void* stream_a, void* stream_b, int* overlap)
 // Synchronises with the device (two 4-byte reads): for logging points and tests, not for the step path.
 // Returns the mask (>= 0), or a negative number if it cannot be read.
 extern "C" int cpc_device_error_flags(int clear) {
-    unsigned a = 0, b = 0, c = 0, d = 0, e = 0, f = 0, g = 0, e2 = 0, h = 0, sn = 0;
+    unsigned a = 0, b = 0, c = 0, d = 0, e = 0, f = 0, g = 0, e2 = 0, h = 0, sn = 0, rn = 0;
     if (cpc::gru_error_flag_fetch(clear, &a) != 0 || cpc::nce_error_flag_fetch(clear, &b) != 0 ||
         cpc::enc_error_flag_fetch(clear, &c) != 0 || cpc::lstm_error_flag_fetch(clear, &d) != 0 ||
         cpc::sup_error_flag_fetch(clear, &e) != 0 || cpc::abx_error_flag_fetch(clear, &f) != 0 ||
         cpc::decode_error_flag_fetch(clear, &g) != 0 || cpc::probe_error_flag_fetch(clear, &e2) != 0 ||
-        cpc::ctc_error_flag_fetch(clear, &h) != 0 || cpc::seqnorm_error_flag_fetch(clear, &sn) != 0) return -1;
+        cpc::ctc_error_flag_fetch(clear, &h) != 0 || cpc::seqnorm_error_flag_fetch(clear, &sn) != 0 ||
+        cpc::rnn_error_flag_fetch(clear, &rn) != 0) return -1;
     e |= e2 | (h & 1u);                                    // ctc_loss.hip: bit 0 labels, bit 1 lengths
     return (int)((a ? 1u : 0u) | (b ? 2u : 0u) | (c ? 4u : 0u) | (d ? 8u : 0u) | (e ? 16u : 0u) | (f ? 32u : 0u) |
-                 (g ? 64u : 0u) | (((h & 2u) || sn) ? 128u : 0u));
+                 (g ? 64u : 0u) | (((h & 2u) || sn) ? 128u : 0u) | (rn ? 256u : 0u));
 }
 
 extern "C" int cpc_get_mfma_mode(void) { return cpc::g_mfma_mode; }

@@ -230,6 +230,7 @@ int abx_error_flag_fetch(int clear, unsigned* out);
 int decode_error_flag_fetch(int clear, unsigned* out);
 int ctc_error_flag_fetch(int clear, unsigned* out);        // ctc_loss.hip: bit 0 CPC_DEVERR_LABEL_RANGE, bit 1 CPC_DEVERR_LENGTH_RANGE
 int seqnorm_error_flag_fetch(int clear, unsigned* out);    // seqnorm.hip: CPC_DEVERR_LENGTH_RANGE
+int rnn_error_flag_fetch(int clear, unsigned* out);        // rnn.hip: CPC_DEVERR_RNN_POLL_TIMEOUT
 
 static inline long align64l(long v) { return (v + 63) & ~63L; }
 

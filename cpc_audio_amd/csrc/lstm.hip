@@ -21,6 +21,9 @@
 //     reductions over the B*S rows afterwards;
 //   * per-step kernels (one launch per step, same MFMA and summation order -- bit-identical) serve grids that cannot be
 //     co-resident and the CPC_LSTM_PER_STEP flag.
+//   * G heads (cpc_lstm_group_*: the criterion's --rnnMode LSTM predictors, cpc/criterion/criterion.py:66-68 -- K one-layer
+//     LSTMs reading the same context) lie side by side in the columns of every (B,S,.) array and ride in blockIdx.z of the same
+//     four kernels: one GEMM projects the input for all heads, as many whole heads as can be resident share a persistent launch.
 #include "cpc_common.h"
 #include "cpc_internal.h"
 #include "gemm_tile.h"
@@ -49,7 +52,19 @@ struct LstmFwd {
     float* hN;            // (B,H) of this layer
     float* cN;            // (B,H) of this layer
     int B, S;
+    // Groups (heads): ng independent recurrences side by side in the columns of every (B,S,.) array -- head g at columns
+    // g * H (g * 4H for gx and G) of rows hs = ng * H (gs = ng * 4H) floats long -- with their W_hh, b_hh one behind the other.
+    // A launch runs the heads g0 + blockIdx.z.  One head: ng = 1, g0 = 0 and the strides are the plain H / 4H.
+    int ng, g0;
+    long hs, gs;
 };
+
+// The pointers of head g0 + blockIdx.z (carried and final state exist for ng == 1 only)
+__device__ __forceinline__ void lstm_fwd_head(LstmFwd& p) {
+    const long g = p.g0 + (int)blockIdx.z;
+    p.gx += g * kLG; p.whh += g * kLG * kLH; p.bhh += g * kLG;
+    p.y += g * kLH; p.G += g * kLG; p.C += g * kLH;
+}
 
 // Lane (i, kq) of wave w holds W_hh[gate * H + j0 + i][koff + 16 ii .. + 4] (koff = 64 w + 4 kq): the B operand of the
 // 16 x 16 x 4 MFMAs for k = koff + 16 ii + jj, as the h fragments of the A operand.
@@ -84,27 +99,28 @@ __device__ __forceinline__ float lstm_fwd_gates(const float (&part)[4][4][256], 
 #pragma unroll
     for (int g = 0; g < 4; ++g)
         pre[g] = (((part[0][g][tid] + part[1][g][tid]) + (part[2][g][tid] + part[3][g][tid])) + p.bhh[g * kLH + j]) +
-                 p.gx[bt * kLG + g * kLH + j];
+                 p.gx[bt * p.gs + g * kLH + j];
     const float ig = sigmoidf_(pre[0]), fg = sigmoidf_(pre[1]), gg = tanhf(pre[2]), og = sigmoidf_(pre[3]);
     c = fmaf(fg, c, ig * gg);
     const float h = og * tanhf(c);
-    float* gs = p.G + bt * kLG + j;
+    float* gs = p.G + bt * p.gs + j;
     gs[0] = ig; gs[kLH] = fg; gs[2 * kLH] = gg; gs[3 * kLH] = og;
-    p.C[bt * kLH + j] = c;
+    p.C[bt * p.hs + j] = c;
     return h;
 }
 
 // h_{t-1} fragments of this lane's row from h0 (t == 0; zeros without it) or from y (plain loads: a finished earlier launch)
 __device__ __forceinline__ void lstm_load_h(float4 (&a)[4], const LstmFwd& p, int b, bool ok, int koff, int t) {
-    const float* src = t == 0 ? (p.h0 ? p.h0 + (long)b * kLH : nullptr) : p.y + ((long)b * p.S + t - 1) * kLH;
+    const float* src = t == 0 ? (p.h0 ? p.h0 + (long)b * kLH : nullptr) : p.y + ((long)b * p.S + t - 1) * p.hs;
 #pragma unroll
     for (int ii = 0; ii < 4; ++ii)
         a[ii] = ok && src ? *reinterpret_cast<const float4*>(src + koff + 16 * ii) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// grid = (H/16, ceil(B/16)), 256 threads; every workgroup resident at once (lstm_persist_fits)
+// grid = (H/16, ceil(B/16), heads), 256 threads; every workgroup resident at once (lstm_heads_per_launch)
 __global__ __launch_bounds__(256) void lstm_persist_fwd_kernel(LstmFwd p, int spin_limit) {
     __shared__ float part[4][4][256];
+    lstm_fwd_head(p);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int i = lane & 15, kq = lane >> 4;
     const int j0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
@@ -121,14 +137,14 @@ __global__ __launch_bounds__(256) void lstm_persist_fwd_kernel(LstmFwd p, int sp
     for (int t = 0; t < p.S; ++t) {
         float4 a[4];
         if (t == 0) lstm_load_h(a, p, arow, ok, koff, 0);
-        else poll_frags<4, 16>(p.y + ((long)arow * p.S + t - 1) * kLH + koff, ok, a, budget, pace, &g_lstm_poll_timeout);
+        else poll_frags<4, 16>(p.y + ((long)arow * p.S + t - 1) * p.hs + koff, ok, a, budget, pace, &g_lstm_poll_timeout);
         lstm_fwd_mfma(part, a, bw, w, i, kq);
         __syncthreads();
         if (live) {
             const long bt = (long)b * p.S + t;
             const float h = lstm_fwd_gates(part, tid, p, bt, j, c);
-            store_coherent(p.y + bt * kLH + j, h);
-            if (t == p.S - 1) {
+            store_coherent(p.y + bt * p.hs + j, h);
+            if (t == p.S - 1 && p.hN) {
                 p.hN[(long)b * kLH + j] = h;
                 p.cN[(long)b * kLH + j] = c;
             }
@@ -140,6 +156,7 @@ __global__ __launch_bounds__(256) void lstm_persist_fwd_kernel(LstmFwd p, int sp
 // One step per launch (grids that cannot be co-resident, CPC_LSTM_PER_STEP): same operands, products and gate math.
 __global__ __launch_bounds__(256) void lstm_step_fwd_kernel(LstmFwd p, int t) {
     __shared__ float part[4][4][256];
+    lstm_fwd_head(p);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int i = lane & 15, kq = lane >> 4;
     const int j0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
@@ -154,10 +171,10 @@ __global__ __launch_bounds__(256) void lstm_step_fwd_kernel(LstmFwd p, int t) {
     const int b = b0 + (tid >> 4), j = j0 + (tid & 15);
     if (b >= p.B) return;
     const long bt = (long)b * p.S + t;
-    float c = t > 0 ? p.C[(bt - 1) * kLH + j] : (p.c0 ? p.c0[(long)b * kLH + j] : 0.f);
+    float c = t > 0 ? p.C[(bt - 1) * p.hs + j] : (p.c0 ? p.c0[(long)b * kLH + j] : 0.f);
     const float h = lstm_fwd_gates(part, tid, p, bt, j, c);
-    p.y[bt * kLH + j] = h;
-    if (t == p.S - 1) {
+    p.y[bt * p.hs + j] = h;
+    if (t == p.S - 1 && p.hN) {
         p.hN[(long)b * kLH + j] = h;
         p.cN[(long)b * kLH + j] = c;
     }
@@ -173,7 +190,15 @@ struct LstmBwd {
     float* dG;            // (B,S,4H) pre-activation gate gradients (persistent launch: pre-filled with kNotReady)
     float* DC;            // (B,H) dc_{t+1} between the launches of the per-step path
     int B, S;
+    int ng, g0;           // heads, as in LstmFwd: W_hh^T and DC of the heads one behind the other
+    long hs, gs;
 };
+
+__device__ __forceinline__ void lstm_bwd_head(LstmBwd& p) {
+    const long g = p.g0 + (int)blockIdx.z;
+    p.whhT += g * kLH * kLG; p.dY += g * kLH; p.G += g * kLG; p.C += g * kLH;
+    p.dG += g * kLG; p.DC += g * p.B * kLH;
+}
 
 // Lane (i, kq) of wave w holds W_hh^T[j0 + i][koff + 16 ii .. + 4], koff = 256 w + 4 kq: its quarter of K = 4H
 __device__ __forceinline__ void lstm_load_whhT(float4 (&bw)[16], const float* __restrict__ whhT, int j0, int i, int koff) {
@@ -198,14 +223,14 @@ __device__ __forceinline__ void lstm_bwd_mfma(float (&part)[4][256], const float
 __device__ __forceinline__ void lstm_bwd_gates(const float (&part)[4][256], int tid, const LstmBwd& p, int b, int j, int t,
                                                float& dc, float (&dg)[4]) {
     const long bt = (long)b * p.S + t;
-    const float dh = ((part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid])) + p.dY[bt * kLH + j];
-    const float* gs = p.G + bt * kLG + j;
+    const float dh = ((part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid])) + p.dY[bt * p.hs + j];
+    const float* gs = p.G + bt * p.gs + j;
     const float ig = gs[0], fg = gs[kLH], gg = gs[2 * kLH], og = gs[3 * kLH];
-    const float c = p.C[bt * kLH + j];
-    const float cp = t > 0 ? p.C[(bt - 1) * kLH + j] : (p.c0 ? p.c0[(long)b * kLH + j] : 0.f);
+    const float c = p.C[bt * p.hs + j];
+    const float cp = t > 0 ? p.C[(bt - 1) * p.hs + j] : (p.c0 ? p.c0[(long)b * kLH + j] : 0.f);
     const float tc = tanhf(c);
     float d = dh * og * (1.0f - tc * tc);
-    if (t + 1 < p.S) d = fmaf(dc, p.G[(bt + 1) * kLG + kLH + j], d);     // + dc_{t+1} * f_{t+1}
+    if (t + 1 < p.S) d = fmaf(dc, p.G[(bt + 1) * p.gs + kLH + j], d);     // + dc_{t+1} * f_{t+1}
     dc = d;
     dg[0] = d * gg * ig * (1.0f - ig);
     dg[1] = d * cp * fg * (1.0f - fg);
@@ -215,6 +240,7 @@ __device__ __forceinline__ void lstm_bwd_gates(const float (&part)[4][256], int 
 
 __global__ __launch_bounds__(256) void lstm_persist_bwd_kernel(LstmBwd p, int spin_limit) {
     __shared__ float part[4][256];
+    lstm_bwd_head(p);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int i = lane & 15, kq = lane >> 4;
     const int j0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
@@ -234,14 +260,14 @@ __global__ __launch_bounds__(256) void lstm_persist_bwd_kernel(LstmBwd p, int sp
 #pragma unroll
             for (int ii = 0; ii < 16; ++ii) a[ii] = make_float4(0.f, 0.f, 0.f, 0.f);
         } else {
-            poll_frags<16, 16>(p.dG + ((long)arow * p.S + t + 1) * kLG + koff, ok, a, budget, pace, &g_lstm_poll_timeout);
+            poll_frags<16, 16>(p.dG + ((long)arow * p.S + t + 1) * p.gs + koff, ok, a, budget, pace, &g_lstm_poll_timeout);
         }
         lstm_bwd_mfma(part, a, bw, w, i, kq);
         __syncthreads();
         if (live) {
             float dg[4];
             lstm_bwd_gates(part, tid, p, b, j, t, dc, dg);
-            float* out = p.dG + ((long)b * p.S + t) * kLG + j;
+            float* out = p.dG + ((long)b * p.S + t) * p.gs + j;
 #pragma unroll
             for (int g = 0; g < 4; ++g) store_coherent(out + g * kLH, dg[g]);
         }
@@ -251,6 +277,7 @@ __global__ __launch_bounds__(256) void lstm_persist_bwd_kernel(LstmBwd p, int sp
 
 __global__ __launch_bounds__(256) void lstm_step_bwd_kernel(LstmBwd p, int t) {
     __shared__ float part[4][256];
+    lstm_bwd_head(p);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int i = lane & 15, kq = lane >> 4;
     const int j0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
@@ -259,7 +286,7 @@ __global__ __launch_bounds__(256) void lstm_step_bwd_kernel(LstmBwd p, int t) {
     lstm_load_whhT(bw, p.whhT, j0, i, koff);
     const bool ok = (b0 + i) < p.B;
     float4 a[16];
-    const float* src = t + 1 < p.S && ok ? p.dG + ((long)(b0 + i) * p.S + t + 1) * kLG + koff : nullptr;
+    const float* src = t + 1 < p.S && ok ? p.dG + ((long)(b0 + i) * p.S + t + 1) * p.gs + koff : nullptr;
 #pragma unroll
     for (int ii = 0; ii < 16; ++ii) a[ii] = src ? *reinterpret_cast<const float4*>(src + 16 * ii) : make_float4(0.f, 0.f, 0.f, 0.f);
     lstm_bwd_mfma(part, a, bw, w, i, kq);
@@ -269,7 +296,7 @@ __global__ __launch_bounds__(256) void lstm_step_bwd_kernel(LstmBwd p, int t) {
     float dc = t + 1 < p.S ? p.DC[(long)b * kLH + j] : 0.f;
     float dg[4];
     lstm_bwd_gates(part, tid, p, b, j, t, dc, dg);
-    float* out = p.dG + ((long)b * p.S + t) * kLG + j;
+    float* out = p.dG + ((long)b * p.S + t) * p.gs + j;
 #pragma unroll
     for (int g = 0; g < 4; ++g) out[g * kLH] = dg[g];
     p.DC[(long)b * kLH + j] = dc;
@@ -310,14 +337,49 @@ static bool lstm_layout(int B, int S, int nl, LstmLayout& g) {
     return true;
 }
 
-// Can all 16 * ceil(B/16) workgroups of the persistent kernel be resident at once?
+// How many whole heads (16 * ceil(B/16) workgroups each) of the persistent kernel can be resident at once?  0: not even one.
+// The occupancy query is advisory and can over-report by one block, and more than 4 blocks of 256 threads per CU are not
+// counted on: resident workgroups = CUs * max(1, min(query - 1, 4)).
 template <class K>
-static bool lstm_persist_fits(K kernel, int B) {
+static int lstm_heads_per_launch(K kernel, int B) {
     int dev = 0, cus = 0, occ = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, 256, 0) != hipSuccess) return false;
-    return 16L * cdiv(B, 16) <= (long)cus * occ;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, 256, 0) != hipSuccess) return 0;
+    const int per_cu = occ - 1 > 4 ? 4 : (occ - 1 < 1 ? 1 : occ - 1);
+    const long fit = (long)cus * per_cu / (16L * cdiv(B, 16));
+    return fit > 64 ? 64 : (int)fit;
+}
+template <class K>
+static bool lstm_persist_fits(K kernel, int B) { return lstm_heads_per_launch(kernel, B) >= 1; }
+
+// The grouped recurrence (cpc_lstm_group_*): every (B,S,.) array holds the G heads side by side
+struct LstmGroupLayout {
+    long G, C, saved_total;
+    long gx, fwd_total;
+    long whhT, wihT, dG, DC, part, tmp, bwd_total;
+};
+
+static bool lstm_group_layout(int B, int S, int G, LstmGroupLayout& g) {
+    if (B <= 0 || S <= 0 || G <= 0 || G > 64) return false;
+    if ((long)B * S > (1L << 21) || (long)B * S * G > (1L << 21)) return false;     // B*S*G*4H floats stay below 2^31
+    const long M = (long)B * S;
+    long o = 0;
+    g.G = o; o += align64l(M * G * kLG);
+    g.C = o; o += align64l(M * G * kLH);
+    g.saved_total = o;
+    g.gx = 0;
+    g.fwd_total = align64l(M * G * kLG);
+    o = 0;
+    g.whhT = o; o += (long)G * kLH * kLG;
+    g.wihT = o; o += (long)G * kLH * kLG;
+    g.dG = o; o += align64l(M * G * kLG);
+    g.DC = o; o += align64l((long)G * B * kLH);
+    const long pa = tn_gemm_part_floats((int)M, G * kLG, kLH), pb = (long)G * tn_gemm_part_floats((int)M, kLG, kLH);
+    g.part = o; o += align64l(pa > pb ? pa : pb);
+    g.tmp = o; o += align64l((long)kRowsSumGroups * G * kLG);
+    g.bwd_total = o;
+    return true;
 }
 
 static bool lstm_ptrs_ok(const float* const* v, int n) {
@@ -365,7 +427,7 @@ extern "C" int cpc_lstm_forward(const float* x, const float* h0, const float* c0
         p.c0 = c0 ? c0 + (long)l * B * kLH : nullptr;
         p.y = out; p.G = saved + g.G[l]; p.C = saved + g.C[l];
         p.hN = hN + (long)l * B * kLH; p.cN = cN + (long)l * B * kLH;
-        p.B = B; p.S = S;
+        p.B = B; p.S = S; p.ng = 1; p.g0 = 0; p.hs = kLH; p.gs = kLG;
         if (persist) {
             if (hipMemsetAsync(out, 0xFF, (size_t)M * kLH * sizeof(float), st) != hipSuccess) return CPC_ERR_ARG;
             hipLaunchKernelGGL(lstm_persist_fwd_kernel, grid, dim3(256), 0, st, p, kLstmSpinLimit);
@@ -405,7 +467,7 @@ extern "C" int cpc_lstm_backward(const float* x, const float* h0, const float* c
         LstmBwd p;
         p.whhT = whhT; p.dY = dYl; p.G = saved + g.G[l]; p.C = saved + g.C[l];
         p.c0 = c0 ? c0 + (long)l * B * kLH : nullptr;
-        p.dG = dG; p.DC = scratch + g.DC; p.B = B; p.S = S;
+        p.dG = dG; p.DC = scratch + g.DC; p.B = B; p.S = S; p.ng = 1; p.g0 = 0; p.hs = kLH; p.gs = kLG;
         if (persist) {
             if (hipMemsetAsync(dG, 0xFF, (size_t)M * kLG * sizeof(float), st) != hipSuccess) return CPC_ERR_ARG;
             hipLaunchKernelGGL(lstm_persist_bwd_kernel, grid, dim3(256), 0, st, p, kLstmSpinLimit);
@@ -438,4 +500,89 @@ extern "C" int cpc_lstm_backward(const float* x, const float* h0, const float* c
         dYl = dXl;
     }
     return 0;
+}
+
+// ---- G heads side by side (the criterion's --rnnMode LSTM predictors): see include/cpc_hip.h
+extern "C" int cpc_lstm_group_layout(int B, int S, int G, long* sizes) {
+    LstmGroupLayout g;
+    CPC_RETURN_IF(!lstm_group_layout(B, S, G, g), CPC_ERR_SHAPE);
+    CPC_RETURN_IF(!sizes, CPC_ERR_ARG);
+    sizes[0] = g.saved_total; sizes[1] = g.fwd_total; sizes[2] = g.bwd_total;
+    return 0;
+}
+
+extern "C" int cpc_lstm_group_forward(const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                                      float* saved, float* scratch, float* y, int B, int S, int G, int flags, void* stream) {
+    LstmGroupLayout g;
+    CPC_RETURN_IF(!lstm_group_layout(B, S, G, g), CPC_ERR_SHAPE);
+    CPC_RETURN_IF(flags & ~CPC_LSTM_PER_STEP, CPC_ERR_ARG);
+    CPC_RETURN_IF(!x || !w_ih || !w_hh || !b_ih || !b_hh || !saved || !scratch || !y, CPC_ERR_ARG);
+    hipStream_t st = (hipStream_t)stream;
+    const int M = B * S;
+    const int fit = (flags & CPC_LSTM_PER_STEP) ? 0 : lstm_heads_per_launch(lstm_persist_fwd_kernel, B);
+    float* gx = scratch + g.gx;
+    int rc = nt_gemm(plain_rows(x, M, kLH), w_ih, kLH, b_ih, gx, (long)G * kLG, G * kLG, kLH, st);   // all heads' input projection
+    if (rc) return rc;
+    LstmFwd p;
+    p.gx = gx; p.whh = w_hh; p.bhh = b_hh; p.h0 = nullptr; p.c0 = nullptr;
+    p.y = y; p.G = saved + g.G; p.C = saved + g.C; p.hN = nullptr; p.cN = nullptr;
+    p.B = B; p.S = S; p.ng = G; p.g0 = 0; p.hs = (long)G * kLH; p.gs = (long)G * kLG;
+    if (fit >= 1) {
+        if (hipMemsetAsync(y, 0xFF, (size_t)M * G * kLH * sizeof(float), st) != hipSuccess) return CPC_ERR_ARG;
+        for (p.g0 = 0; p.g0 < G; p.g0 += fit)       // as many whole heads per launch as can be resident together
+            hipLaunchKernelGGL(lstm_persist_fwd_kernel, dim3(kLH / 16, cdiv(B, 16), G - p.g0 < fit ? G - p.g0 : fit), dim3(256), 0,
+                               st, p, kLstmSpinLimit);
+    } else {
+        for (int t = 0; t < S; ++t)
+            hipLaunchKernelGGL(lstm_step_fwd_kernel, dim3(kLH / 16, cdiv(B, 16), G), dim3(256), 0, st, p, t);
+    }
+    CPC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cpc_lstm_group_backward(const float* x, const float* w_ih, const float* w_hh, const float* saved, const float* y,
+                                       const float* dy, float* scratch, float* dx, float* dw_ih, float* dw_hh, float* db_ih,
+                                       float* db_hh, int B, int S, int G, int flags, void* stream) {
+    LstmGroupLayout g;
+    CPC_RETURN_IF(!lstm_group_layout(B, S, G, g), CPC_ERR_SHAPE);
+    CPC_RETURN_IF(flags & ~CPC_LSTM_PER_STEP, CPC_ERR_ARG);
+    CPC_RETURN_IF(!x || !w_ih || !w_hh || !saved || !y || !dy || !scratch || !dx || !dw_ih || !dw_hh || !db_ih || !db_hh,
+                  CPC_ERR_ARG);
+    hipStream_t st = (hipStream_t)stream;
+    const int M = B * S;
+    const int fit = (flags & CPC_LSTM_PER_STEP) ? 0 : lstm_heads_per_launch(lstm_persist_bwd_kernel, B);
+    float* whhT = scratch + g.whhT, *wihT = scratch + g.wihT, *dG = scratch + g.dG;
+    int rc = transpose(w_hh, whhT, kLG, kLH, st, G, (long)kLG * kLH, (long)kLG * kLH);      // per head (4H,H) -> (H,4H)
+    if (rc) return rc;
+    rc = transpose(w_ih, wihT, G * kLG, kLH, st);                                           // stacked (G 4H,H) -> (H,G 4H)
+    if (rc) return rc;
+    LstmBwd p;
+    p.whhT = whhT; p.dY = dy; p.G = saved + g.G; p.C = saved + g.C; p.c0 = nullptr;
+    p.dG = dG; p.DC = scratch + g.DC; p.B = B; p.S = S; p.ng = G; p.g0 = 0; p.hs = (long)G * kLH; p.gs = (long)G * kLG;
+    if (fit >= 1) {
+        if (hipMemsetAsync(dG, 0xFF, (size_t)M * G * kLG * sizeof(float), st) != hipSuccess) return CPC_ERR_ARG;
+        for (p.g0 = 0; p.g0 < G; p.g0 += fit)
+            hipLaunchKernelGGL(lstm_persist_bwd_kernel, dim3(kLH / 16, cdiv(B, 16), G - p.g0 < fit ? G - p.g0 : fit), dim3(256), 0,
+                               st, p, kLstmSpinLimit);
+    } else {
+        for (int t = S - 1; t >= 0; --t)
+            hipLaunchKernelGGL(lstm_step_bwd_kernel, dim3(kLH / 16, cdiv(B, 16), G), dim3(256), 0, st, p, t);
+    }
+    CPC_LAUNCH_CHECK();
+    // stacked dW_ih = dG^T . x and both bias gradients over all heads' gate columns at once; dW_hh head by head in one launch
+    const RowMap gm = plain_rows(dG, M, G * kLG);
+    rc = tn_gemm(gm, G * kLG, plain_rows(x, M, kLH), kLH, scratch + g.part, dw_ih, 0, st);
+    if (rc) return rc;
+    RowMap hm;                                           // h_{t-1} rows of head 0: y[b, t-1, 0:H] (zero row at t = 0)
+    hm.base = y; hm.R = S; hm.bstride = (long)S * G * kLH; hm.rstride = G * kLH; hm.off = -G * kLH;
+    hm.tmul = 1; hm.tadd = -1; hm.Lin = S; hm.M = M;
+    GemmGroup grp;
+    grp.G = G; grp.a = kLG; grp.b = kLH; grp.c = (long)kLG * kLH;
+    rc = tn_gemm(gm, kLG, hm, kLH, scratch + g.part, dw_hh, 0, st, GemmBounds(), grp);
+    if (rc) return rc;
+    rc = rows_sum(dG, M, G * kLG, scratch + g.tmp, db_ih, st);
+    if (rc) return rc;
+    rc = rows_sum(dG, M, G * kLG, scratch + g.tmp, db_hh, st);
+    if (rc) return rc;
+    return nt_gemm(gm, wihT, G * kLG, nullptr, dx, kLH, kLH, G * kLG, st);     // dx = sum over heads of dG_g . W_ih,g
 }

@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .ops import EncoderFunction, GruFunction, LstmFunction
+from .ops import EncoderFunction, GruFunction, LstmFunction, RnnFunction
 
 
 class ChannelNorm(nn.Module):
@@ -168,14 +168,19 @@ class CPCAR(nn.Module):
     autoregressors -- ``LSTM`` (its argparse default, cpc_default_config.py:74), ``RNN``, other widths -- run through baseNet's
     own torch forward: same semantics incl. the carried hidden state, any device, not the hot path.
     ``lstmKernel=True`` (not in the reference's signature; default off) runs the LSTM of 256 -> 256 through cpc_lstm_forward
-    (HIP, ``self.hip_lstm``) for CUDA fp32 input; baseNet stays the nn.LSTM parameter container.  ``self.hip`` keeps meaning
-    the GRU kernel (what the fused train step checks)."""
+    (HIP, ``self.hip_lstm``) for CUDA fp32 input; baseNet stays the nn.LSTM parameter container.  ``rnnKernel=True`` does the same
+    for mode ``RNN``: nn.RNN(256, 256, nLevelsGRU, batch_first=True) of 1..8 layers through cpc_rnn_forward (HIP,
+    ``self.hip_rnn``), baseNet the nn.RNN parameter container.  ``self.hip`` keeps meaning the GRU kernel (what the fused train
+    step checks)."""
 
-    def __init__(self, dimEncoded, dimOutput, keepHidden, nLevelsGRU, mode="GRU", reverse=False, lstmKernel=False):
+    def __init__(self, dimEncoded, dimOutput, keepHidden, nLevelsGRU, mode="GRU", reverse=False, lstmKernel=False,
+                 rnnKernel=False):
         super().__init__()
         self.RESIDUAL_STD = 0.1
         self.hip = mode not in ("LSTM", "RNN") and dimEncoded == 256 and dimOutput == 256
         self.hip_lstm = bool(lstmKernel) and mode == "LSTM" and dimEncoded == 256 and dimOutput == 256
+        self.hip_rnn = (bool(rnnKernel) and mode == "RNN" and dimEncoded == 256 and dimOutput == 256
+                        and 1 <= nLevelsGRU <= 8)
         cell = nn.LSTM if mode == "LSTM" else (nn.RNN if mode == "RNN" else nn.GRU)
         self.baseNet = cell(dimEncoded, dimOutput, num_layers=nLevelsGRU, batch_first=True)
         self.hidden = None
@@ -203,6 +208,13 @@ class CPCAR(nn.Module):
             # |h_t| = |o * tanh(c_t)| <= 1 at every step whatever (h0, c0) is: unlike the GRU, whose h_t mixes in h_{t-1},
             # the output never carries the initial state through, so no check of where self.hidden came from is needed
             out._cpc_abs_bound = 1.0
+            return out
+        if self.hip_rnn and x.is_cuda and x.dtype == torch.float32:
+            y, hN = RnnFunction.apply(flip(x), self.hidden, False, False, *self._flat_params())
+            if self.keepHidden:
+                self.hidden = hN.detach()
+            out = flip(y)
+            out._cpc_abs_bound = 1.0                           # |tanh| <= 1 whatever h0 is
             return out
         if not self.hip:                                       # cpc/model.py:185-204 with baseNet's own torch forward
             y, h = self.baseNet(flip(x), self.hidden)

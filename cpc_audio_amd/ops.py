@@ -65,6 +65,9 @@ def check_device_errors(clear=True):
     if mask & 128:
         what.append("the phone classifier's CTC loss or seqNorm received an input or target length outside its range (it was "
                     "clamped; that sequence's loss is NaN)")
+    if mask & 256:
+        what.append("a workgroup of a persistent Elman RNN recurrence timed out waiting for its neighbours "
+                    "(outputs contain NaN from that step on)")
     if what:
         raise _lib.CpcHipError("device-side error: " + "; ".join(what))
 
@@ -569,6 +572,125 @@ def lstm_supported(B, S, nl=1):
     """Does cpc_lstm_layout take nl layers on (B, S, 256)?"""
     try:
         _layout("lstm_layout", _lib.get().cpc_lstm_layout, 3, int(B), int(S), int(nl))
+    except ValueError:
+        return False
+    return True
+
+
+class LstmGroupFunction(torch.autograd.Function):
+    """x (B,S,256) read by every head; the heads' nn.LSTM parameters one behind the other: w_ih (G*1024,256), w_hh (G,1024,256),
+    b_ih, b_hh (G*1024) -> y (B,S,G*256), head g at columns g*256.. (cpc_lstm_group_forward / _backward): one layer, no carried
+    state.  per_step: the one-launch-per-step kernels instead of the persistent recurrence (same bits; tests)."""
+
+    @staticmethod
+    def forward(ctx, x, per_step, w_ih, w_hh, b_ih, b_hh):
+        _require_cuda(x, "LstmGroupFunction")
+        lib = _lib.get()
+        if (x.dim() != 3 or x.shape[2] != _HID or w_hh.dim() != 3 or tuple(w_hh.shape[1:]) != (4 * _HID, _HID)
+                or tuple(w_ih.shape) != (w_hh.shape[0] * 4 * _HID, _HID) or b_ih.numel() != w_ih.shape[0]
+                or b_hh.numel() != w_ih.shape[0]):
+            raise NotImplementedError("cpc_audio_amd.LstmGroupFunction: x (B,S,256) and G stacked nn.LSTM(256, 256) parameters expected")
+        B, S, _ = x.shape
+        G = w_hh.shape[0]
+        x = x.contiguous()
+        w_ih, w_hh, b_ih, b_hh = (p.detach().contiguous() for p in (w_ih, w_hh, b_ih, b_hh))
+        flags = 1 if per_step else 0                      # CPC_LSTM_PER_STEP
+        with torch.cuda.device(x.device):
+            sizes = _layout("lstm_group_layout", lib.cpc_lstm_group_layout, 3, B, S, G)
+            saved = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
+            scratch = torch.empty(sizes[1], device=x.device, dtype=torch.float32)
+            y = torch.empty(B, S, G * _HID, device=x.device, dtype=torch.float32)
+            lib.check(lib.cpc_lstm_group_forward(_p(x), _p(w_ih), _p(w_hh), _p(b_ih), _p(b_hh), _p(saved), _p(scratch), _p(y),
+                                                 B, S, G, flags, _stream()), "lstm_group_forward")
+        ctx.save_for_backward(x, saved, y, w_ih, w_hh, b_ih)
+        ctx.dims = (B, S, G, sizes[2], flags)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if dy is None:
+            return (None,) * 6
+        lib = _lib.get()
+        x, saved, y, w_ih, w_hh, b_ih = ctx.saved_tensors
+        B, S, G, nscr, flags = ctx.dims
+        with torch.cuda.device(x.device):
+            scratch = torch.empty(nscr, device=x.device, dtype=torch.float32)
+            dx = torch.empty_like(x)
+            dw_ih, dw_hh, db_ih, db_hh = (torch.empty_like(t) for t in (w_ih, w_hh, b_ih, b_ih))
+            lib.check(lib.cpc_lstm_group_backward(_p(x), _p(w_ih), _p(w_hh), _p(saved), _p(y), _p(dy.contiguous()), _p(scratch),
+                                                  _p(dx), _p(dw_ih), _p(dw_hh), _p(db_ih), _p(db_hh), B, S, G, flags, _stream()),
+                      "lstm_group_backward")
+        return dx, None, dw_ih, dw_hh, db_ih, db_hh
+
+
+def lstm_group_supported(B, S, G):
+    """Does cpc_lstm_group_layout take G heads on (B, S, 256)?"""
+    try:
+        _layout("lstm_group_layout", _lib.get().cpc_lstm_group_layout, 3, int(B), int(S), int(G))
+    except ValueError:
+        return False
+    return True
+
+
+class RnnFunction(torch.autograd.Function):
+    """Elman recurrences, nn.RNN(256, 256) with tanh (cpc_rnn_forward / _backward).  ``time_major``: x (T,R,256) -> y (T,R,G*256),
+    head g at columns g*256.. -- the criterion's RNN predictors, which walk the batch axis of the context; otherwise x (R,T,256)
+    -> y (R,T,G*256) -- the batch_first autoregressor (G = 1).  params: per layer weight_ih (G*256,256), weight_hh (G,256,256) or
+    (256,256), bias_ih, bias_hh (G*256): the heads' tensors one behind the other; G > 1 only with one layer and without h0.
+    h0: None or (nl,R,256); it receives no gradient (the reference detaches the carried state, cpc/model.py:194-198).
+    -> y, hN (nl,R,256; not differentiable; None for G > 1).  per_step: one launch per step (same bits; tests)."""
+
+    @staticmethod
+    def forward(ctx, x, h0, time_major, per_step, *params):
+        _require_cuda(x, "RnnFunction")
+        lib = _lib.get()
+        nl = len(params) // 4
+        if (x.dim() != 3 or x.shape[2] != _HID or nl < 1 or len(params) != 4 * nl or params[0].shape[0] % _HID
+                or any(tuple(params[4 * l].shape) != tuple(params[0].shape) or params[4 * l].shape[1] != _HID
+                       or params[4 * l + 1].numel() != params[0].numel() or params[4 * l + 2].numel() != params[0].shape[0]
+                       or params[4 * l + 3].numel() != params[0].shape[0] for l in range(nl))):
+            raise NotImplementedError("cpc_audio_amd.RnnFunction: x (.,.,256) and stacked nn.RNN(256, 256) parameters expected")
+        G = params[0].shape[0] // _HID
+        T, R = (x.shape[0], x.shape[1]) if time_major else (x.shape[1], x.shape[0])
+        x = x.contiguous()
+        params = [p.detach().contiguous() for p in params]
+        h0 = None if h0 is None else h0.detach().contiguous()
+        flags = (1 if per_step else 0) | (2 if time_major else 0)       # CPC_RNN_PER_STEP, CPC_RNN_TIME_MAJOR
+        with torch.cuda.device(x.device):
+            sizes = _layout("rnn_layout", lib.cpc_rnn_layout, 3, T, R, G, nl)
+            saved = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
+            scratch = torch.empty(sizes[1], device=x.device, dtype=torch.float32)
+            y = torch.empty(x.shape[0], x.shape[1], G * _HID, device=x.device, dtype=torch.float32)
+            hN = torch.empty(nl, R, _HID, device=x.device, dtype=torch.float32) if G == 1 else None
+            lib.check(lib.cpc_rnn_forward(_p(x), _p(h0), _ptrs(params), _p(saved), _p(scratch), _p(y), _p(hN), T, R, G, nl, flags,
+                                          _stream()), "rnn_forward")
+        ctx.save_for_backward(x, saved, y, *params)
+        ctx.h0 = h0
+        ctx.dims = (T, R, G, nl, sizes[2], flags)
+        if hN is not None:
+            ctx.mark_non_differentiable(hN)
+        ctx.set_materialize_grads(False)
+        return y, hN
+
+    @staticmethod
+    def backward(ctx, dy, _dhN):
+        lib = _lib.get()
+        x, saved, y, *params = ctx.saved_tensors
+        T, R, G, nl, nscr, flags = ctx.dims
+        dy = torch.zeros_like(y) if dy is None else dy.contiguous()
+        with torch.cuda.device(x.device):
+            scratch = torch.empty(nscr, device=x.device, dtype=torch.float32)
+            dx = torch.empty_like(x)
+            grads = [torch.empty_like(p) for p in params]
+            lib.check(lib.cpc_rnn_backward(_p(x), _p(ctx.h0), _ptrs(params), _p(saved), _p(y), _p(dy), _p(scratch), _p(dx),
+                                           _ptrs(grads), T, R, G, nl, flags, _stream()), "rnn_backward")
+        return (dx, None, None, None, *grads)
+
+
+def rnn_supported(T, R, G=1, nl=1):
+    """Does cpc_rnn_layout take T steps of R rows, G heads and nl layers?"""
+    try:
+        _layout("rnn_layout", _lib.get().cpc_rnn_layout, 3, int(T), int(R), int(G), int(nl))
     except ValueError:
         return False
     return True

@@ -12,10 +12,10 @@ from .optim import Adam
 
 
 def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False, reverse=False, arMode="GRU",
-                sizeWindow=20480, abspos=False, transformerDropout=0.1, lstmKernel=False, encoder_type="cpc"):
+                sizeWindow=20480, abspos=False, transformerDropout=0.1, lstmKernel=False, encoder_type="cpc", rnnKernel=False):
     """cpc/feature_loader.py:124-153 (getEncoder / getAR) + cpc/train.py:311.  arMode 'GRU' (north star) or
     'transformer' (BASELINE.json config 4: buildTransformerAR(hiddenEncoder, 1, sizeWindow // 160, abspos)); 'LSTM' /
-    'RNN' as the reference (lstmKernel: the LSTM on the HIP kernels, CPCAR); 'no_ar': the identity, and the context width is
+    'RNN' as the reference (lstmKernel / rnnKernel: the LSTM / the RNN on the HIP kernels, CPCAR); 'no_ar': the identity, and the context width is
     the encoder's (cpc/train.py:486).  encoder_type 'cpc' or 'lfb' (learned filter banks, LFBEnconder); 'mfcc' needs
     torchaudio and is not built here."""
     if encoder_type == "mfcc":
@@ -30,7 +30,8 @@ def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False
         from .transformers import buildTransformerAR
         ar = buildTransformerAR(hiddenEncoder, 1, sizeWindow // 160, abspos, dropout=transformerDropout)
     else:
-        ar = CPCAR(hiddenEncoder, hiddenGar, keepHidden, nLevelsGRU, mode=arMode, reverse=reverse, lstmKernel=lstmKernel)
+        ar = CPCAR(hiddenEncoder, hiddenGar, keepHidden, nLevelsGRU, mode=arMode, reverse=reverse, lstmKernel=lstmKernel,
+                   rnnKernel=rnnKernel)
     return CPCModel(enc, ar)
 
 

@@ -83,6 +83,9 @@ int cpc_get_mfma_mode(void);
 #define CPC_DEVERR_ABX_INDEX 32
 #define CPC_DEVERR_DECODE_RANGE 64
 #define CPC_DEVERR_LENGTH_RANGE 128
+/*   CPC_DEVERR_RNN_POLL_TIMEOUT  a workgroup of a persistent Elman recurrence (cpc_rnn_forward / _backward) gave up waiting for
+ *                                another one; its outputs carry NaN from that step on */
+#define CPC_DEVERR_RNN_POLL_TIMEOUT 256
 int cpc_device_error_flags(int clear);
 
 /* ---------------------------------------------------------------- encoder ----
@@ -321,6 +324,46 @@ int cpc_lstm_forward(const float* x, const float* h0, const float* c0, const flo
 int cpc_lstm_backward(const float* x, const float* h0, const float* c0, const float* const* params, const float* saved,
                       const float* y, const float* dy, float* scratch, float* dx, float* const* grads, int B, int S, int nl,
                       int flags, void* stream);
+
+/* G LSTM heads side by side (the criterion's --rnnMode LSTM: K nn.LSTM(256, 256, batch_first=True) reading the same context,
+ * cpc/criterion/criterion.py:66-68): one layer, no carried state, 1 <= G <= 64, B * S * G <= 2^21, fp32.
+ * x, dx: (B,S,256), shared by the heads (dx is summed over them); y, dy: (B,S,G*256), head g at columns g*256.. -- the layout the
+ * score kernels read.  The heads' parameters one behind the other: w_ih (G*1024,256), w_hh (G,1024,256), b_ih, b_hh (G*1024), gate
+ * rows i,f,g,o; the gradients have the same layouts and are OVERWRITTEN.
+ * cpc_lstm_group_layout fills sizes[0..2] = saved / forward-scratch / backward-scratch floats.
+ * The input projection of all heads is one GEMM; the recurrences of as many whole heads as can be resident together (counted as
+ * CUs * max(1, min(occupancy query - 1, 4)) workgroups) share one persistent launch, the launches follow one another; where not
+ * even one head fits, and with CPC_LSTM_PER_STEP, one launch per time step runs all heads.  Same bits either way.  A polling
+ * time-out raises CPC_DEVERR_LSTM_POLL_TIMEOUT.  Arguments are checked before any launch. */
+int cpc_lstm_group_layout(int B, int S, int G, long* sizes);
+int cpc_lstm_group_forward(const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                           float* saved, float* scratch, float* y, int B, int S, int G, int flags, void* stream);
+int cpc_lstm_group_backward(const float* x, const float* w_ih, const float* w_hh, const float* saved, const float* y,
+                            const float* dy, float* scratch, float* dx, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh,
+                            int B, int S, int G, int flags, void* stream);
+
+/* ------------------------------------------------------------ Elman RNN ----
+ * torch.nn.RNN(256, 256) with tanh: h_t = tanh(W_ih x_t + b_ih + W_hh h_{t-1} + b_hh), over T time steps of R independent rows,
+ * G heads side by side and nl stacked layers, fp32; T * R * G <= 2^21, 1 <= G <= 64, 1 <= nl <= 8, and G > 1 only with nl == 1
+ * and without h0 / hN (CPC_ERR_SHAPE / CPC_ERR_ARG otherwise).
+ * flags: CPC_RNN_TIME_MAJOR: x, dx are (T,R,256) and y, dy (T,R,G*256) -- the criterion's --rnnMode RNN predictors, whose nn.RNN
+ *   is built without batch_first and so walks the batch axis of the (B,W,256) context: T = B, R = W, G = K
+ *   (cpc/criterion/criterion.py:62-64); without it they are (R,T,256) / (R,T,G*256) -- CPCAR with mode "RNN"
+ *   (cpc/model.py:177-180: nn.RNN(256, 256, nl, batch_first=True)), R = B, T = S, G = 1.
+ *   CPC_RNN_PER_STEP: one launch per time step instead of the persistent recurrence (otherwise taken for as many whole heads per
+ *   launch as can be resident together, as cpc_lstm_group_forward); same bits.
+ * params / grads: for l = 0..nl-1 weight_ih_l (G*256,256), weight_hh_l (G,256,256), bias_ih_l, bias_hh_l (G*256): the heads' tensors
+ *   one behind the other; grads are OVERWRITTEN.  h0 (or NULL), hN (or NULL): (nl,R,256); h0 receives no gradient.
+ * cpc_rnn_layout fills sizes[0..2] = saved / forward-scratch / backward-scratch floats.  The backward needs y and `saved` (the
+ * lower layers' outputs) only.  A polling time-out raises CPC_DEVERR_RNN_POLL_TIMEOUT.  Arguments are checked before any launch. */
+#define CPC_RNN_PER_STEP 1
+#define CPC_RNN_TIME_MAJOR 2
+int cpc_rnn_layout(int T, int R, int G, int nl, long* sizes);
+int cpc_rnn_forward(const float* x, const float* h0, const float* const* params, float* saved, float* scratch, float* y, float* hN,
+                    int T, int R, int G, int nl, int flags, void* stream);
+int cpc_rnn_backward(const float* x, const float* h0, const float* const* params, const float* saved, const float* y,
+                     const float* dy, float* scratch, float* dx, float* const* grads, int T, int R, int G, int nl, int flags,
+                     void* stream);
 
 /* ------------------------------------------------------------ supervised criteria ----
  * SpeakerCriterion / PhoneCriterion (cpc/criterion/criterion.py:182-246): nn.Linear(256, C) + nn.CrossEntropyLoss() (mean)

@@ -1,6 +1,7 @@
-"""Time the feed-forward prediction networks (--rnnMode ffd / conv4 / conv8 / conv12) on an MI355X: the criterion's forward +
-backward with ``hipPredictors`` on (csrc/pred_conv.hip) and off (the torch modules: per head a transpose, a pad, one MIOpen
-Conv1d, a multiply, a transpose back, then one cat -- the parent's path) on the same GPU, same commit, same process.
+"""Time the prediction networks behind ``hipPredictors`` (--rnnMode ffd / conv4 / conv8 / conv12 / RNN / LSTM) on an MI355X: the
+criterion's forward + backward with the flag on (csrc/pred_conv.hip; csrc/rnn.hip, csrc/lstm.hip) and off (the torch modules:
+per head a transpose, a pad, one MIOpen Conv1d, a multiply, a transpose back -- or one nn.RNN / nn.LSTM call -- then one cat: the
+parent's path) on the same GPU, same commit, same process.
 
     python tools/bench_predictors.py [--rounds 9] [--iters 5] [--out profiles/bench_predictors.json]
 
@@ -8,7 +9,8 @@ B = 64, S = 128 (W = 116), K = 12, N = 128: CPCUnsupersivedCriterion(rnnMode)(c,
 ranges; one call = forward, losses.sum().backward() with gradients to c, z and every predictor parameter.  The two paths
 alternate round by round after a warm-up; a round times ``iters`` calls between two device events.  Per mode and path the JSON
 holds the median over the rounds, the fastest and slowest round and the spread (max - min) / median; per mode the predictors'
-algorithmic FLOPs from the shapes (forward 2 K B W 256 256 ks, backward twice that), the ratio torch / HIP with ``won`` = the
+algorithmic FLOPs from the shapes (forward 2 K B W 256 256 ks, backward twice that; ks = 2 for RNN, 8 for LSTM: the input and
+recurrent products of one and of four gates), the ratio torch / HIP with ``won`` = the
 HIP path's slowest round is faster than the torch path's fastest; and the mean shader clock and socket power sampled in process
 during each mode's timed rounds (bench.RsmiSampler; None where the library is missing).  The times are whole criterion steps
 (predictors + score kernels), so ``predictor_tflops_if_all_time`` UNDERSTATES the predictor kernels' own rate."""
@@ -26,7 +28,7 @@ from bench import RsmiSampler  # noqa: E402
 from cpc_audio_amd.train import build_criterion  # noqa: E402
 
 B, S, K, N = 64, 128, 12, 128
-TAPS = {"ffd": 2, "conv4": 4, "conv8": 8, "conv12": 12}          # 256 x 256 products per head and frame
+TAPS = {"ffd": 2, "conv4": 4, "conv8": 8, "conv12": 12, "RNN": 2, "LSTM": 8}          # 256 x 256 products per head and frame
 ROOF_TFLOPS = 157.0        # exact-f32 MFMA (v_mfma_f32_32x32x2_f32), the arithmetic of csrc/pred_conv.hip
 
 
