@@ -11,7 +11,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libcpc_hip.so")
 DEFAULT_GRU_MODE = 2       # cpc_set_gru_mode: persistent recurrence, forward products on the fp16 split
-DEFAULT_GRU_XCD_LOCAL = 1  # cpc_set_gru_xcd_local: forward hand-over through one XCD's L2 for batches of at most half the device (round 6)
+DEFAULT_GRU_XCD_LOCAL = 3  # cpc_set_gru_xcd_local: hand-over through one XCD's L2 -- forward per batch tile (round 6), backward per (tile, layer) group
 DEFAULT_GRU_POLL_PLAIN = 15  # cpc_set_gru_poll_plain: every first look of the persistent recurrence through the XCD's L2 (round 6)
 DEFAULT_MFMA_MODE = 3      # what libcpc_hip starts in (cpc_set_mfma_mode): mode 2's arithmetic (two fp16 pieces, 3 MFMAs per
 #                            product) with conv1 / its gradients on the DMA-fed kernels reading H2-stored activations

@@ -193,8 +193,8 @@ struct Gru2Fwd {
     int tile0, total_tiles;    // persistent launch only: this launch covers batch tiles [tile0, tile0 + ntiles) of total_tiles
     int first_sleep;           // persistent launch only: see PollPace (< 0: self-steering)
     int poll_plain;            // persistent launch only: which waves take their FIRST look with plain (L2-cached) loads (cpc_set_gru_poll_plain)
-    unsigned* xsync;           // persistent launch only: NULL, or two words per batch tile (0xFFFFFFFF) for the placement check of the
-                               // XCD-local hand-over (tile_on_one_xcd; cpc_set_gru_xcd_local)
+    unsigned* xsync;           // persistent launch only: NULL, or four words per batch tile (0xFFFFFFFF; the forward uses two) for the
+                               // placement check of the XCD-local hand-over (on_one_xcd; cpc_set_gru_xcd_local)
 };
 
 // Component-wise f32x4 arithmetic on MFMA accumulators written out scalar by scalar: f32x4 operators compile to v_pk_{add,mul}_f32,
@@ -325,14 +325,16 @@ struct Gru2Bwd {
     const float* cr[2]; const float* cz[2]; const float* cnh[2]; const float* cni[2];   // see gru_bwd_coef_kernel
     float* dGi[2]; float* dGh[2]; float* DH[2];
     float* xdh[2];             // persistent launch only: hand-over copies of DH[l] (fragment order)
+    float* xdh1r;              // persistent launch with the (tile, layer) group numbering only, else NULL: a second copy of xdh[1],
+                               // always stored device scope, for layer 0's look across the XCDs (persist_bwd)
     int B, S;
     int spin_limit;            // persistent launch only: polling budget of a wave (cpc_set_gru_spin_limit)
     int ntiles, xcd_pack;      // persistent launch only: see PersistIds
     int tile0, total_tiles;    // persistent launch only: this launch covers batch tiles [tile0, tile0 + ntiles) of total_tiles
     int first_sleep;           // persistent launch only: see PollPace (< 0: self-steering)
     int poll_plain;            // persistent launch only: which waves take their FIRST look with plain (L2-cached) loads (cpc_set_gru_poll_plain)
-    unsigned* xsync;           // persistent launch only: NULL, or two words per batch tile (0xFFFFFFFF) for the placement check of the
-                               // XCD-local hand-over (tile_on_one_xcd; cpc_set_gru_xcd_local)
+    unsigned* xsync;           // persistent launch only: NULL, or four words per batch tile (0xFFFFFFFF) for the placement check of the
+                               // XCD-local hand-over (on_one_xcd; cpc_set_gru_xcd_local)
 };
 
 // Everything in the gate derivatives that does not depend on dh, for all (b, t, j) at once and in fragment
@@ -497,18 +499,32 @@ static __device__ unsigned g_gru_poll_timeout = 0;
 // every tile checks it once, at the start of the launch: each workgroup clears the bit of its XCC_ID in a word of ones and counts
 // itself in (device scope), waits for the other 31, and the tile takes the local path only if exactly one bit went.  A tile that
 // straddles XCDs -- or a wait that runs out of budget -- keeps the device-scope stores: correct either way.
+// The backward's unit is smaller (kPackGroup): the per-step all-to-all is among the 16 workgroups of one (tile, layer) group, which
+// check their placement the same way with two words of their own (`members` = 16); see persist_bwd for the one look that crosses.
 __device__ __forceinline__ void store_handover(float* p, float v, bool local) {
     if (local) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ bool tile_on_one_xcd(unsigned* sync, int spin_limit) {
+// this workgroup's XCD: hwreg(HW_REG_XCC_ID), bits 3:0.  The host emulator has no XCDs and reports 0 for every workgroup; with
+// HIPEMU_XCDS=n in the environment (read at every launch, so a test may change it between launches) it places workgroup b on
+// XCD b % n instead: n = 8 is the placement the packed numberings assume, any other n > 1 makes the checks below find a straddle.
+__device__ __forceinline__ unsigned xcc_id() {
+#ifdef HIPEMU
+    const char* e = getenv("HIPEMU_XCDS");
+    const int n = e ? atoi(e) : 0;
+    return n > 1 ? (unsigned)(blockIdx.x % (unsigned)n) & 15u : 0u;
+#else
+    return __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;
+#endif
+}
+__device__ __forceinline__ bool on_one_xcd(unsigned* sync, int spin_limit, unsigned members) {
     __shared__ unsigned verdict;
     if (threadIdx.x == 0) {
-        const unsigned xid = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;       // hwreg(HW_REG_XCC_ID), bits 3:0
+        const unsigned xid = xcc_id();
         __hip_atomic_fetch_and(sync, ~(1u << xid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(sync + 1, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);     // 0xFFFFFFFF + 32 arrivals = 31
+        __hip_atomic_fetch_add(sync + 1, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);     // 0xFFFFFFFF + n arrivals = n - 1
         int budget = spin_limit < 4096 ? spin_limit : 4096;
-        while (__hip_atomic_load(sync + 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 31u && budget-- > 0) __builtin_amdgcn_s_sleep(8);
+        while (__hip_atomic_load(sync + 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != members - 1u && budget-- > 0) __builtin_amdgcn_s_sleep(8);
         const unsigned gone = ~__hip_atomic_load(sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         verdict = (budget > 0 && gone != 0u && (gone & (gone - 1u)) == 0u) ? 1u : 0u;
     }
@@ -639,19 +655,13 @@ struct PersistIds {
     // grid is 256 * ceil(G / 8) and tile (slot / 32) * 8 + xcd takes the 32 slots of its XCD -- every hand-over of a tile
     // then stays inside one L2 instead of crossing the fabric (surplus workgroups exit at once; at B = 64 four XCDs
     // run the recurrence and four are left to the side-stream kernels).  Otherwise (default, faster): grid = 32 G, ids of one
-    // tile G apart.
+    // tile G apart.  pack == kPackGroup (backward): the same per (tile, layer slot) group of 16 workgroups -- persist.h.
     // A launch may cover only the batch tiles [tile0, tile0 + G) of `total` (a batch too large for one resident grid runs as
     // several launches one after the other: sequences are independent); everything is addressed by the global tile.
     __device__ PersistIds(int G, int pack, int tile0, int total) {
-        int rest;
-        if (pack) {
-            const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-            tile = (slot >> 5) * 8 + xcd;
-            rest = slot & 31;
-        } else {
-            tile = blockIdx.x % G;
-            rest = blockIdx.x / G;
-        }
+        const PersistSlot s = persist_slot((int)blockIdx.x, G, pack);
+        const int rest = s.rest;
+        tile = s.tile;
         valid = tile < G && tile0 + tile < total;
         tile += tile0;
         ntiles = total;
@@ -845,7 +855,7 @@ __global__ __launch_bounds__(kPersistThreads) void gru2_persist_fwd_kernel(Gru2F
     __shared__ float part[2][8][3][256];
     const PersistIds id(p.ntiles, p.xcd_pack, p.tile0, p.total_tiles);
     if (!id.valid) return;
-    const bool local = p.xsync != nullptr && tile_on_one_xcd(p.xsync + 2 * id.tile, p.spin_limit);
+    const bool local = p.xsync != nullptr && on_one_xcd(p.xsync + 4 * id.tile, p.spin_limit, 32u);
     if (id.layer == 0) persist_fwd<0, false, NT>(p, part, id, local);
     else persist_fwd<1, false, NT>(p, part, id, local);
 }
@@ -855,7 +865,7 @@ __global__ __launch_bounds__(kPersistThreads) void gru2_persist_fwd_h2_kernel(Gr
     __shared__ float part[2][8][3][256];
     const PersistIds id(p.ntiles, p.xcd_pack, p.tile0, p.total_tiles);
     if (!id.valid) return;
-    const bool local = p.xsync != nullptr && tile_on_one_xcd(p.xsync + 2 * id.tile, p.spin_limit);
+    const bool local = p.xsync != nullptr && on_one_xcd(p.xsync + 4 * id.tile, p.spin_limit, 32u);
     if (id.layer == 0) persist_fwd<0, true, NT>(p, part, id, local);
     else persist_fwd<1, true, NT>(p, part, id, local);
 }
@@ -879,6 +889,11 @@ __device__ __forceinline__ void load_coef(float4 (&cf)[NU][3], const float* __re
 // (The fp16-split products of the forward, mfma_gates_h2, were tried here too -- with a per-wave, per-step power-of-two
 // scale taken from the operand's own max, since gate gradients have no a-priori bound: parity was fine, but the extra
 // VALU work (max, scale, 48 conversions per lane and step) and 23 spilled registers made the step 0.23 ms slower.)
+// Locality.  The per-step all-to-all is inside one layer of one tile: the 16 workgroups of (tile, LAYER) poll each other's xdh[LAYER]
+// fragments of step t + 1.  The only look across the layers is layer 0's waves 4-7 at layer 1's dh of the same step, and layer 1
+// does not depend on layer 0 here, so it runs ahead and that look is off the chain.  With the group numbering (kPackGroup) a group
+// that on_one_xcd finds on one XCD therefore stores PLAIN to xdh[LAYER] (`local`), and layer 1 adds a device-scope copy in xdh1r
+// for layer 0 whether it went local or not (layer 0 cannot know): same floats in both, nothing else changes.
 // NT: batch tiles per workgroup, as in persist_fwd.  With NT = 2 the coefficients of a step are requested together with its
 // first poll instead of one step ahead (two prefetched sets would not fit the register budget of three waves per SIMD); the
 // other tile's work hides them.
@@ -910,7 +925,8 @@ __device__ __forceinline__ void persist_bwd(const Gru2Bwd& p, float (&part)[2][8
         const float* __restrict__ c1 = p.cz[sl];
         const float* __restrict__ c2 = recurrent ? p.cnh[sl] : p.cni[sl];
         const long lane_off = xpos(i, unit0);
-        const float* __restrict__ xsrc = p.xdh[sl] + lane_off;
+        // (group numbering: layer 1's group may keep xdh[1] in its own XCD's L2 -- the look across the layers takes the device-scope copy)
+        const float* __restrict__ xsrc = (!recurrent && p.xdh1r ? p.xdh1r : p.xdh[sl]) + lane_off;
         bool tok[NT], bok[NT];
 #pragma unroll
         for (int k = 0; k < NT; ++k) {
@@ -1018,6 +1034,9 @@ __device__ __forceinline__ void persist_bwd(const Gru2Bwd& p, float (&part)[2][8
             const float dh = (((pt[0][e] + pt[1][e]) + (pt[2][e] + pt[3][e])) +
                               ((pt[4][e] + pt[5][e]) + (pt[6][e] + pt[7][e]))) + dh0;
             store_handover(p.xdh[LAYER] + xtile(t, tl[k], id.ntiles, kH) + xp, dh, local);   // first: others wait for it
+            // group numbering: layer 0 sits on another XCD and would not find a line that is dirty in this one's L2, so its copy goes
+            // out device scope -- behind the store the group's own chain waits for; layer 0 reads it steps later as a rule
+            if (LAYER == 1 && p.xdh1r) store_coherent(p.xdh1r + xtile(t, tl[k], id.ntiles, kH) + xp, dh);
             pc.lap(4, traced);
             float* gi = p.dGi[LAYER] + bt * kG;
             float* gh = p.dGh[LAYER] + bt * kG;
@@ -1043,7 +1062,9 @@ __global__ __launch_bounds__(kPersistThreads) void gru2_persist_bwd_kernel(Gru2B
     __shared__ float part[2][8][256];
     const PersistIds id(p.ntiles, p.xcd_pack, p.tile0, p.total_tiles);
     if (!id.valid) return;
-    const bool local = p.xsync != nullptr && tile_on_one_xcd(p.xsync + 2 * id.tile, p.spin_limit);
+    // placement check per batch tile (32 workgroups), or per (tile, layer slot) group of 16 with words of its own
+    const bool group = p.xcd_pack == kPackGroup;
+    const bool local = p.xsync != nullptr && on_one_xcd(p.xsync + 4 * id.tile + (group ? 2 * id.layer : 0), p.spin_limit, group ? 16u : 32u);
     if (id.layer == 0) persist_bwd<1, NT>(p, part, id, local);    // the top layer leads
     else persist_bwd<0, NT>(p, part, id, local);
 }
@@ -1055,10 +1076,13 @@ struct GruLayout {
     long gi, xh, xh_floats, fwd_total;       // forward scratch (xh: hand-over buffers of the persistent launch)
     long whhT, wihT, dGi, dGh, DH, mid[2], part, tmp;
     long whhT2, wihT2, dGi2, dGh2, DH2;      // second set for the two-layer wavefront
-    long coef, xdh, frag_floats;             // two-layer path: 8 coefficient arrays, 2 hand-over buffers (fragment order)
-    long sync_floats;                        // ... and, behind either pair of hand-over buffers, two words per batch tile (tile_on_one_xcd)
+    long coef, xdh, frag_floats;             // two-layer path: 8 coefficient arrays, 3 hand-over buffers (fragment order: xdh[0], xdh[1], xdh1r)
+    long sync_floats;                        // ... and, behind either set of hand-over buffers, four words per batch tile (on_one_xcd)
     long bwd_total;
 };
+
+constexpr int kXdhBufs = 3;                  // hand-over buffers of the persistent backward: xdh[0], xdh[1], xdh1r
+constexpr int kCoefBufs = 8 + kXdhBufs;      // fragment-ordered arrays at the head of the `coef` buffer (cpc_gru_coef_floats)
 
 static bool gru_layout(int B, int S, int nl, GruLayout& g) {
     if (B <= 0 || S <= 0 || nl <= 0 || nl > 8) return false;
@@ -1077,7 +1101,7 @@ static bool gru_layout(int B, int S, int nl, GruLayout& g) {
     g.gi = 0;
     g.xh = align64l((long)B * S * kG);
     g.xh_floats = nl == 2 ? align64l((long)S * tiles16 * kH) : 0;
-    g.sync_floats = nl == 2 ? align64l(2L * cdiv(B, 16)) : 0;
+    g.sync_floats = nl == 2 ? align64l(4L * cdiv(B, 16)) : 0;
     g.fwd_total = g.xh + 2 * g.xh_floats + g.sync_floats;
     o = 0;
     g.whhT = o; o += (long)kH * kG;
@@ -1096,7 +1120,7 @@ static bool gru_layout(int B, int S, int nl, GruLayout& g) {
     g.DH2 = o; o += bsh;
     g.frag_floats = nl == 2 ? align64l((long)S * tiles16 * kH) : 0;
     g.coef = o; o += 8 * g.frag_floats;
-    g.xdh = o; o += 2 * g.frag_floats + g.sync_floats;
+    g.xdh = o; o += kXdhBufs * g.frag_floats + g.sync_floats;
     g.bwd_total = o;
     return true;
 }
@@ -1109,12 +1133,18 @@ namespace {
 int g_gru_spin_limit = kSpinLimit;
 int g_gru_first_sleep[2] = {-1, -1};   // forward, backward (cpc_set_gru_poll_pacing); < 0: self-steering
 int g_gru_poll_plain = 15; // cpc_set_gru_poll_plain
-int g_gru_xcd_local = 1;   // cpc_set_gru_xcd_local: bit 0 forward, bit 1 backward (launches with one batch tile per workgroup: B <= 128
-                           // on MI355X), bits 2 / 3 the same for any launch
-// (defaults from profiles/r6_ab_gru_handover.txt, MI355X: B = 64 forward alone 317 -> 272 us with the local hand-over and plain
-//  first looks, B = 128 351 -> 290, step at B = 64 2.77 -> 2.71 ms; the backward -- which runs beside the criterion's dz path -- gains
-//  from the plain first looks only and LOSES with the packed numbering in the step (2.84 ms); with two tiles per workgroup
-//  (B = 256) the local forward loses (518 -> 583 us) and so do the backward's plain looks (1620 -> 1758 us): both stay off there)
+int g_gru_xcd_local = 3;   // cpc_set_gru_xcd_local: bit 0 forward (one batch tile per XCD), bit 1 backward (one (tile, layer) group of 16
+                           // workgroups per half XCD) in launches with one batch tile per workgroup (B <= 128 on MI355X); bits 2 / 3 the
+                           // same for any launch (the backward then per tile where a workgroup owns two)
+// (forward, profiles/r6_ab_gru_handover.txt, MI355X: B = 64 alone 317 -> 272 us with the local hand-over and plain first looks,
+//  B = 128 351 -> 290, step at B = 64 2.77 -> 2.71 ms.  Backward, which runs beside the criterion's dz path: one TILE per XCD lost
+//  in the step (2.84 against 2.78 ms) -- four tiles x 32 workgroups fill four whole XCDs and leave nce_bwd_g_kernel, which is
+//  gather-bound, half the chip's L2s.  One (tile, layer) GROUP per XCD -- the unit of the backward's per-step all-to-all, persist_bwd
+//  -- takes 16 of every XCD's 32 CUs, the same 128 / 128 split as the unpacked launch, and all eight L2s stay in use:
+//  profiles/ab_gru_bwd_layer_groups.txt, B = 64: the launch in the step 544 -> 454 us, nce_bwd_g_kernel beside it 328 -> 305 us,
+//  the step 2.656 -> 2.606 ms (three alternations, every run below every run of the parent); the backward call alone 699 -> 633 us,
+//  at B = 128 969 -> 849 us.  With two tiles per workgroup (B = 256) the local forward loses (518 -> 583 us) and so do the
+//  backward's plain looks (1620 -> 1758 us): both stay off there)
 int g_gru_xcd_pack = 0;    // persistent launches: 0 (default) = tiles interleaved over the XCDs, 1 = one batch tile per XCD where the
                            // device has 8 (PersistIds; measured slower: B = 64 forward +42 us, backward +70 us -- what a tile gains
                            // in hand-over distance it loses to 32 instead of 16 polling workgroups on its L2), 2 = packed numbering
@@ -1124,9 +1154,10 @@ int g_gru_mode = 2;        // 0: per-step launches; 1: persistent two-layer recu
                            // split, 3 MFMAs per product; exact-f32 when the caller supplies h0, whose size is unknown)
 
 // Grid of a persistent launch over G batch tiles (PersistIds), or 0 if its 32 G working workgroups (kPersistThreads each)
-// cannot all be resident at once.  *pack: one tile per XCD -- when asked for (g_gru_xcd_pack 1) and the device is 8 XCDs of
-// cus / 8 CUs each with room for 32 * ceil(G / 8) workgroups per XCD; g_gru_xcd_pack == 2 forces the packed numbering on any
-// device whose dispatcher hands out workgroups in id order as slots free up (the emulator; surplus ids exit at once).
+// cannot all be resident at once.  *pack: the numbering (persist.h) -- a packed one when asked for (g_gru_xcd_pack 1, or the XCD-local
+// hand-over: kPackTile forward, kPackGroup backward) and the device is 8 XCDs of cus / 8 CUs each with room for the slots the
+// numbering gives every XCD (persist_pack_fits); g_gru_xcd_pack == 2 forces the packed numbering that is asked for (kPackTile if
+// none is) on any device whose dispatcher hands out workgroups in id order as slots free up (the emulator; surplus ids exit at once).
 // Batch tiles per persistent launch: all of them if their 32 G workgroups can be resident together, else the largest
 // count that can (0: not even one tile).  g_gru_chunk_tiles > 0 caps it (tests: chunking on a device that would not need it).
 int g_gru_chunk_tiles = 0;
@@ -1156,20 +1187,25 @@ static bool xcd_local_wanted(int dirbit, int NT) {
     if (g_gru_xcd_local & (4 << dirbit)) return true;
     return (g_gru_xcd_local & (1 << dirbit)) && NT == 1;
 }
+// The backward's numbering: kPackGroup -- (tile, layer) groups of 16 workgroups, the unit of its per-step all-to-all -- in launches
+// with one batch tile per workgroup (bit 1, or bit 3); launches with two tiles per workgroup keep the tile numbering (bit 3 only).
+static int bwd_pack_wanted(int NT) {
+    if (NT == 1 && (g_gru_xcd_local & (2 | 8))) return kPackGroup;
+    return (g_gru_xcd_local & 8) ? kPackTile : kPackNone;
+}
+// want: the numbering the caller would like (kPackNone / kPackTile / kPackGroup); *pack: the one the launch gets -- a packed
+// numbering only where every XCD has room for the workgroups it assumes there (persist_pack_fits), else the unpacked launch.
 template <class K>
-int persist_grid(K kernel, int G, int* pack, bool want_pack = false) {
+int persist_grid(K kernel, int G, int* pack, int want = kPackNone) {
     int dev = 0, cus = 0, occ = 0;
-    *pack = 0;
+    *pack = kPackNone;
     if (hipGetDevice(&dev) != hipSuccess) return 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, kPersistThreads, 0) != hipSuccess) return 0;
-    const long room = (long)cus * occ;
-    if (32L * G > room) return 0;
-    if (g_gru_xcd_pack == 2 || ((g_gru_xcd_pack == 1 || want_pack) && cus % 8 == 0 && 32L * cdiv(G, 8) <= (long)(cus / 8) * occ)) {
-        *pack = 1;
-        return 256 * cdiv(G, 8);
-    }
-    return 32 * G;
+    if (!persist_pack_fits(G, kPackNone, cus, occ)) return 0;
+    if (want == kPackNone && g_gru_xcd_pack >= 1) want = kPackTile;
+    if (want != kPackNone && (g_gru_xcd_pack == 2 || persist_pack_fits(G, want, cus, occ))) *pack = want;
+    return persist_grid_size(G, *pack);
 }
 }  // namespace
 
@@ -1223,10 +1259,13 @@ extern "C" int cpc_set_gru_poll_plain(int mask) {
     return 0;
 }
 
-// XCD-local hand-over of the persistent recurrence (store_handover / tile_on_one_xcd): bit 0 the forward launch, bit 1 the backward
-// launch take the packed numbering (one batch tile per XCD, where the device has 8 with room for it) and, tile by tile, plain
-// stores when the placement check finds the tile's 32 workgroups on one XCD -- in launches with one batch tile per workgroup
-// (the measured win); bits 2 / 3: in any launch.  Same bits as the device-scope hand-over.  Default 1.
+// XCD-local hand-over of the persistent recurrence (store_handover / on_one_xcd): bit 0 the forward launch takes the packed
+// numbering (one batch tile per XCD, where the device has 8 with room for it) and, tile by tile, plain stores when the placement
+// check finds the tile's 32 workgroups on one XCD; bit 1 the backward launch takes the group numbering (the 16 workgroups of a
+// (tile, layer) group on one XCD, two or more groups per XCD beyond 8; the unpacked launch where the device cannot host it)
+// and, group by group, plain stores inside the group plus layer 1's device-scope copy for layer 0 -- both in launches with one
+// batch tile per workgroup (the measured win); bits 2 / 3: in any launch (a backward whose workgroups own two tiles keeps the
+// numbering per tile).  Same bits as the device-scope hand-over.  Default 3.
 extern "C" int cpc_set_gru_xcd_local(int mask) {
     if (mask < 0 || mask > 15) return CPC_ERR_ARG;
     g_gru_xcd_local = mask;
@@ -1326,10 +1365,10 @@ static int gru_forward_impl(const float* x, const float* h0, const float* const*
             persist_plan(p.total_tiles, fit1, fit2, &p.ntiles, &NT);
         }
         const int nblocks = g_gru_mode < 1 || p.ntiles <= 0 ? 0
-                            : h2 ? (NT == 2 ? persist_grid(gru2_persist_fwd_h2_kernel<2>, p.ntiles, &p.xcd_pack, xcd_local_wanted(0, NT))
-                                            : persist_grid(gru2_persist_fwd_h2_kernel<1>, p.ntiles, &p.xcd_pack, xcd_local_wanted(0, NT)))
-                                 : (NT == 2 ? persist_grid(gru2_persist_fwd_kernel<2>, p.ntiles, &p.xcd_pack, xcd_local_wanted(0, NT))
-                                            : persist_grid(gru2_persist_fwd_kernel<1>, p.ntiles, &p.xcd_pack, xcd_local_wanted(0, NT)));
+                            : h2 ? (NT == 2 ? persist_grid(gru2_persist_fwd_h2_kernel<2>, p.ntiles, &p.xcd_pack, xcd_local_wanted(0, NT) ? kPackTile : kPackNone)
+                                            : persist_grid(gru2_persist_fwd_h2_kernel<1>, p.ntiles, &p.xcd_pack, xcd_local_wanted(0, NT) ? kPackTile : kPackNone))
+                                 : (NT == 2 ? persist_grid(gru2_persist_fwd_kernel<2>, p.ntiles, &p.xcd_pack, xcd_local_wanted(0, NT) ? kPackTile : kPackNone)
+                                            : persist_grid(gru2_persist_fwd_kernel<1>, p.ntiles, &p.xcd_pack, xcd_local_wanted(0, NT) ? kPackTile : kPackNone));
         if (nblocks > 0) {
             p.xh[0] = scratch + g.xh; p.xh[1] = scratch + g.xh + g.xh_floats;
             if (coef) { p.coef[0] = coef; p.coef[1] = coef + 4 * g.frag_floats; }
@@ -1379,8 +1418,9 @@ static int gru_forward_impl(const float* x, const float* h0, const float* const*
 extern "C" long cpc_gru_coef_floats(int B, int S, int nl) {
     GruLayout g;
     if (nl != 2 || !gru_layout(B, S, nl, g)) return 0;
-    // 8 coefficient arrays + the two hand-over buffers of the persistent backward + the four transposed weight matrices
-    return 10 * g.frag_floats + g.sync_floats + 4L * kG * kH;
+    // 8 coefficient arrays + the three hand-over buffers of the persistent backward and its placement words + the four transposed
+    // weight matrices
+    return kCoefBufs * g.frag_floats + g.sync_floats + 4L * kG * kH;
 }
 
 static void launch_gru_coef(const GruLayout& g, const float* h0, const float* saved, const float* y, float* coef,
@@ -1406,14 +1446,14 @@ extern "C" int cpc_gru_backward_coef(const float* h0, const float* const* params
     CPC_RETURN_IF(!params || !saved || !y || !coef, CPC_ERR_ARG);
     if (!coef_done) launch_gru_coef(g, h0, saved, y, coef, B, S, (hipStream_t)stream);     // (else: cpc_gru_forward_coef wrote them)
     {   // (3H,H) -> (H,3H), the four weight matrices in one launch: W_hh0, W_ih0, W_hh1, W_ih1 behind the hand-over buffers
-        float* wT = coef + 10 * g.frag_floats + g.sync_floats;
+        float* wT = coef + kCoefBufs * g.frag_floats + g.sync_floats;
         const float* tin[4] = {params[1], params[0], params[5], params[4]};
         float* tout[4] = {wT, wT + (long)kG * kH, wT + 2L * kG * kH, wT + 3L * kG * kH};
         int rc = transpose_batch(tin, tout, 4, kG, kH, (hipStream_t)stream);
         if (rc) return rc;
     }
     // ... and the hand-over buffers of the persistent backward, pre-filled with the "not written yet" pattern
-    if (hipMemsetAsync(coef + 8 * g.frag_floats, 0xFF, (2 * g.frag_floats + g.sync_floats) * sizeof(float), (hipStream_t)stream) != hipSuccess)
+    if (hipMemsetAsync(coef + 8 * g.frag_floats, 0xFF, (kXdhBufs * g.frag_floats + g.sync_floats) * sizeof(float), (hipStream_t)stream) != hipSuccess)
         return CPC_ERR_ARG;
     CPC_LAUNCH_CHECK();
     return 0;
@@ -1451,7 +1491,7 @@ extern "C" int cpc_gru_backward_streams(const float* x, const float* h0, const f
     const int M = B * S;
     if (nl == 2) {                                   // two-layer wavefront (see gru2_bwd_kernel)
         // (the transposed weights come with `coef` when the caller prepared it, cpc_gru_backward_coef)
-        float* cwT = coef ? const_cast<float*>(coef) + 10 * g.frag_floats + g.sync_floats : nullptr;
+        float* cwT = coef ? const_cast<float*>(coef) + kCoefBufs * g.frag_floats + g.sync_floats : nullptr;
         float* whhT_[2] = {coef ? cwT : scratch + g.whhT, coef ? cwT + 2L * kG * kH : scratch + g.whhT2};
         float* wihT_[2] = {coef ? cwT + (long)kG * kH : scratch + g.wihT, coef ? cwT + 3L * kG * kH : scratch + g.wihT2};
         float* dGi_[2] = {scratch + g.dGi, scratch + g.dGi2};
@@ -1481,6 +1521,7 @@ extern "C" int cpc_gru_backward_streams(const float* x, const float* h0, const f
         if (!coef) launch_gru_coef(g, h0, saved, y, scratch + g.coef, B, S, st);
         p.wih1T = wihT_[1];
         p.xsync = nullptr;
+        p.xdh1r = nullptr;
         p.total_tiles = cdiv(B, 16);
         p.tile0 = 0;
         int NT = 1;
@@ -1488,11 +1529,12 @@ extern "C" int cpc_gru_backward_streams(const float* x, const float* h0, const f
                      persist_chunk((const void*)gru2_persist_bwd_kernel<2>, p.total_tiles), &p.ntiles, &NT);
         if (NT == 2 && !(g_gru_poll_plain & 16)) p.poll_plain = 0;     // two tiles per workgroup: the backward's plain looks lose
         const int nblocks = g_gru_mode < 1 || p.ntiles <= 0 ? 0
-                            : NT == 2 ? persist_grid(gru2_persist_bwd_kernel<2>, p.ntiles, &p.xcd_pack, xcd_local_wanted(1, NT))
-                                      : persist_grid(gru2_persist_bwd_kernel<1>, p.ntiles, &p.xcd_pack, xcd_local_wanted(1, NT));
+                            : NT == 2 ? persist_grid(gru2_persist_bwd_kernel<2>, p.ntiles, &p.xcd_pack, bwd_pack_wanted(NT))
+                                      : persist_grid(gru2_persist_bwd_kernel<1>, p.ntiles, &p.xcd_pack, bwd_pack_wanted(NT));
         if (nblocks > 0) {
-            if (!coef && hipMemsetAsync(p.xdh[0], 0xFF, (2 * g.frag_floats + g.sync_floats) * sizeof(float), st) != hipSuccess) return CPC_ERR_ARG;
-            p.xsync = xcd_local_wanted(1, NT) && p.xcd_pack ? reinterpret_cast<unsigned*>(p.xdh[0] + 2 * g.frag_floats) : nullptr;
+            if (!coef && hipMemsetAsync(p.xdh[0], 0xFF, (kXdhBufs * g.frag_floats + g.sync_floats) * sizeof(float), st) != hipSuccess) return CPC_ERR_ARG;
+            p.xsync = bwd_pack_wanted(NT) && p.xcd_pack ? reinterpret_cast<unsigned*>(p.xdh[0] + kXdhBufs * g.frag_floats) : nullptr;
+            if (p.xcd_pack == kPackGroup) p.xdh1r = p.xdh[0] + 2 * g.frag_floats;
             // (in-step timing: the marker in FRONT of this launch is recorded by cpc_train_step before it releases the side
             // stream's gather kernels -- a marker packet between that release and this launch lets their workgroups take the
             // CUs first, and the persistent launch then waits 250 us for residency: measured)

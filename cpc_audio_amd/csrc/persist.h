@@ -103,4 +103,41 @@ __device__ __forceinline__ void poll_frags(const float* __restrict__ row, bool o
     }
 }
 
+// Workgroup numberings of a persistent two-layer launch over G batch tiles of 32 workgroups each (2 layer slots x 16 unit
+// tiles; gru.hip: PersistIds), shared by the kernels and by the host code that sizes the grid and checks residency.
+//   kPackNone   grid 32 G, the ids of one tile G apart (tiles interleaved over the XCDs)
+//   kPackTile   workgroup b goes to XCD b % 8 (the dispatcher's round-robin on an idle device): tile (slot / 32) * 8 + xcd
+//               takes 32 consecutive slots of its XCD, grid 256 ceil(G / 8)
+//   kPackGroup  the same per (tile, layer slot) GROUP of 16 workgroups: group g = 2 tile + slot takes 16 consecutive slots of
+//               XCD g % 8, grid 128 ceil(2 G / 8); beyond 8 groups an XCD hosts group g, g + 8, ... one after the other
+// Ids whose tile is >= G are surplus and exit at once.
+constexpr int kPackNone = 0, kPackTile = 1, kPackGroup = 2;
+struct PersistSlot { int tile, rest; };              // rest = layer slot * 16 + unit tile
+__host__ __device__ inline PersistSlot persist_slot(int bid, int G, int pack) {
+    PersistSlot s;
+    const int xcd = bid & 7, slot = bid >> 3;
+    if (pack == kPackGroup) {
+        const int group = (slot >> 4) * 8 + xcd;
+        s.tile = group >> 1;
+        s.rest = (group & 1) * 16 + (slot & 15);
+    } else if (pack == kPackTile) {
+        s.tile = (slot >> 5) * 8 + xcd;
+        s.rest = slot & 31;
+    } else {
+        s.tile = bid % G;
+        s.rest = bid / G;
+    }
+    return s;
+}
+__host__ __device__ inline int persist_grid_size(int G, int pack) {
+    return pack == kPackGroup ? 128 * ((2 * G + 7) / 8) : pack == kPackTile ? 256 * ((G + 7) / 8) : 32 * G;
+}
+// can a device of `cus` CUs (8 XCDs of cus / 8) with `occ` workgroups per CU keep every working workgroup of the packed
+// numbering resident, each on the XCD the numbering assumes?
+__host__ __device__ inline bool persist_pack_fits(int G, int pack, int cus, int occ) {
+    if (pack == kPackNone) return 32L * G <= (long)cus * occ;
+    if (cus <= 0 || cus % 8 != 0) return false;
+    return (long)(persist_grid_size(G, pack) / 8) <= (long)(cus / 8) * occ;
+}
+
 }  // namespace cpc
