@@ -140,6 +140,9 @@ SIGNATURES = {
     "cpc_lfb_energy_backward": (_I, [_P] * 8 + [_I, _I, _I, _P]),
     "cpc_lfb_lognorm_forward": (_I, [_P] * 3 + [_I, _I, _I, _I, _P]),
     "cpc_lfb_lognorm_backward": (_I, [_P] * 4 + [_I, _I, _I, _I, _P]),
+    "cpc_mfcc_layout": (_I, [_I, _I, _I, _P]),
+    "cpc_mfcc_meldb": (_I, [_P] * 5 + [_I, _I, _I, _P]),
+    "cpc_mfcc_dct": (_I, [_P] * 4 + [_I, _I, _I, _I, _P]),
     "cpc_pred_conv_layout": (_I, [_I, _I, _I, _I, _P]),
     "cpc_pred_conv_forward": (_I, [_P] * 5 + [_I] * 5 + [_F, _I, _P]),
     "cpc_pred_conv_backward": (_I, [_P] * 8 + [_I] * 5 + [_F, _I, _P]),

@@ -635,7 +635,8 @@ def _checkpoint_feature_function(args):
     model = train.build_model(hiddenEncoder=saved.get("hiddenEncoder", 256), hiddenGar=saved.get("hiddenGar", 256),
                               nLevelsGRU=saved.get("nLevelsGRU", 1), arMode=saved.get("arMode", "LSTM"),
                               reverse=saved.get("cpc_mode") == "reverse", sizeWindow=saved.get("sizeWindow", 20480),
-                              abspos=saved.get("abspos", False), encoder_type=saved.get("encoder_type", "cpc"))
+                              abspos=saved.get("abspos", False), encoder_type=saved.get("encoder_type", "cpc"),
+                              mfccKernel=True)
     harness.load_checkpoint(str(ckpt), model)
     model.gAR.keepHidden = True
     maker = harness.FeatureModule(model, args.get_encoded).cuda().eval()

@@ -462,7 +462,8 @@ def load_feature_maker(path_checkpoint, no_pretraining=False, in_dim=1):
     model = train.build_model(hiddenEncoder=saved.get("hiddenEncoder", 256), hiddenGar=saved.get("hiddenGar", 256),
                               nLevelsGRU=saved.get("nLevelsGRU", 1), arMode=saved.get("arMode", "LSTM"),
                               reverse=saved.get("cpc_mode") == "reverse", sizeWindow=saved.get("sizeWindow", 20480),
-                              abspos=saved.get("abspos", False), encoder_type=saved.get("encoder_type", "cpc"))
+                              abspos=saved.get("abspos", False), encoder_type=saved.get("encoder_type", "cpc"),
+                              mfccKernel=True)
     if not no_pretraining:
         harness.load_checkpoint(str(ckpt), model)
     width = saved.get("hiddenEncoder", 256) if saved.get("arMode", "LSTM") == "no_ar" else saved.get("hiddenGar", 256)

@@ -363,7 +363,11 @@ class FeatureModule(torch.nn.Module):
         return self.featureMaker.gEncoder.DOWNSAMPLING
 
     def _device(self):
-        return next(self.featureMaker.parameters()).device
+        for t in self.featureMaker.parameters():
+            return t.device
+        for t in self.featureMaker.buffers():             # (MFCCEncoder + NoAr: tables, no parameters)
+            return t.device
+        return torch.device("cpu")
 
     def forward(self, data):
         waves, label = data
@@ -488,7 +492,7 @@ def loadModel(pathCheckpoints):
     read from THAT directory's checkpoint_args.json; the state dict is loaded (strict=False) from the path given.  Arguments
     missing from the file take the reference's defaults (cpc_default_config.py); the autoregressor carries its state from
     call to call when samplingType is "sequential", as getAR builds it.  ``encoder_type`` 'lfb' and ``arMode`` 'no_ar' build LFBEnconder / NoAr
-    (hiddenGar is then the encoder's width, cpc/train.py:486); 'mfcc' raises NotImplementedError.  Concatenated models -- more than one checkpoint at
+    (hiddenGar is then the encoder's width, cpc/train.py:486); 'mfcc' builds MFCCEncoder (build_model's mfccKernel).  Concatenated models -- more than one checkpoint at
     either level -- raise ValueError."""
     from .train import build_model
     if len(pathCheckpoints) != 1:
@@ -501,7 +505,7 @@ def loadModel(pathCheckpoints):
     model = build_model(hiddenEncoder=hiddenEncoder, hiddenGar=hiddenGar, nLevelsGRU=saved.get("nLevelsGRU", 1),
                         keepHidden=saved.get("samplingType", "samespeaker") == "sequential",
                         reverse=saved.get("cpc_mode") == "reverse", arMode=arMode, sizeWindow=saved.get("sizeWindow", 20480),
-                        abspos=saved.get("abspos", False), encoder_type=saved.get("encoder_type", "cpc"))
+                        abspos=saved.get("abspos", False), encoder_type=saved.get("encoder_type", "cpc"), mfccKernel=True)
     print(f"Loading the state dict at {path}")
     model.load_state_dict(torch.load(path, map_location="cpu")["gEncoder"], strict=False)
     return model, hiddenGar, hiddenEncoder
@@ -537,23 +541,44 @@ def build_feature(feature_maker, seq, strict=False, max_size_seq=64000, seq_norm
     ``seq`` of shape (1, n_samples).  Device-first: the file crosses to the GPU once, all equally long chunks go through
     the model as ONE batch (the encoder and a stateless autoregressor see a chunk the same whether it arrives alone or as
     row i of a batch; up to ``max_batch`` rows per launch), per-chunk time normalisation and the strict tail cut are batched
-    tensor ops, the pieces are joined on the device and the result crosses back once.  Only when the autoregressor carries
+    tensor ops, the pieces are joined on the device and the result crosses back once.  An MFCCEncoder floors its decibels
+    80 dB below the maximum of the whole CALL: it runs with ``topPerRow`` set for the duration, so that a batched call gives what
+    the reference's chunk-by-chunk calls give.  Only when the autoregressor carries
     its state from chunk to chunk (``gAR.keepHidden``, cpc/eval/ABX.py:170) -- or the module flattens its output -- do the
     chunks go through one after the other, still without leaving the device.  Returns (1, n_frames, feature_dim) on the CPU."""
     n = seq.size(1)
     try:
         device = next(feature_maker.parameters()).device
-    except (AttributeError, StopIteration):
+    except AttributeError:
         device = seq.device
+    except StopIteration:                     # no parameters (MFCCEncoder + NoAr): where the tables live
+        device = next((t.device for t in feature_maker.buffers()), seq.device)
     wave = seq.reshape(-1).to(device, non_blocking=True)
     plan = chunk_plan(n, max_size_seq, strict, feature_maker.getDownsamplingFactor())
     ar = getattr(getattr(feature_maker, "featureMaker", None), "gAR", None)
     one_by_one = bool(getattr(ar, "keepHidden", False)) or bool(getattr(feature_maker, "collapse", False))
+    from .model import MFCCEncoder
+    mfcc = getattr(getattr(feature_maker, "featureMaker", None), "gEncoder", None)
+    mfcc = mfcc if isinstance(mfcc, MFCCEncoder) else None
+    scope = None if mfcc is None else mfcc.topPerRow
 
     def features(rows):                       # rows: (k, chunk length) waveform windows -> (k, frames, dim)
         f = feature_maker((rows.unsqueeze(1), None))
         return seq_normalization(f) if seq_norm else f
 
+    if mfcc is not None:
+        mfcc.topPerRow = True
+    try:
+        pieces = _feature_pieces(features, wave, plan, one_by_one, max_batch)
+    finally:
+        if mfcc is not None:
+            mfcc.topPerRow = scope
+    out = pieces[0] if len(pieces) == 1 else torch.cat(pieces, dim=1)
+    return out.cpu()
+
+
+def _feature_pieces(features, wave, plan, one_by_one, max_batch):
+    """build_feature's walk over the chunk plan: -> the list of (1, frames, dim) pieces on the device."""
     pieces = []
     with torch.no_grad():
         i = 0
@@ -569,5 +594,4 @@ def build_feature(feature_maker, seq, strict=False, max_size_seq=64000, seq_norm
                 f = f[:, -keep:]              # (keep == 0 keeps everything, as the reference's slice does)
             pieces.append(f.reshape(1, -1, f.size(-1)))
             i += k
-    out = pieces[0] if len(pieces) == 1 else torch.cat(pieces, dim=1)
-    return out.cpu()
+    return pieces

@@ -147,6 +147,93 @@ class LFBEnconder(nn.Module):
         return x if self.instancenorm is None else self.instancenorm(x)
 
 
+class MFCCEncoder(nn.Module):
+    """cpc/model.py:108-122 (--encoder_type mfcc): the reference's hand-made baseline,
+    torchaudio.transforms.MFCC(n_mfcc=dimEncoded, melkwargs={"n_mels": max(128, dimEncoded), "n_fft": 321}) followed by its
+    permute -- restated here from torchaudio's documented defaults (sample rate 16 kHz, periodic Hann window of 321 points, hop
+    160, centred frames with reflect padding, power spectrum, HTK mel scale over the grid linspace(0, 8000, 161) without area
+    normalisation, 10 log10 with a floor 80 dB below the maximum of the WHOLE input tensor, orthonormal DCT-II), because
+    torchaudio is not a dependency of this package.  The restatement matches torchaudio's documented formula; it has not been
+    compared with an installed torchaudio.
+
+    The tables are buffers under the names torchaudio gives them, so that a reference checkpoint loads into them:
+    ``MFCC.MelSpectrogram.spectrogram.window`` (321), ``MFCC.MelSpectrogram.mel_scale.fb`` (161, M) and ``MFCC.dct_mat`` (M, D).
+    These names are written from memory of torchaudio's modules and are unverified; every load in this package is strict=False,
+    so a mismatch cannot break one.  ``basis`` (321, 322), the windowed DFT basis the kernel reads, is a non-persistent buffer
+    derived from ``window``; it is rebuilt when a state dict is loaded.  There are no parameters and the waveform receives no
+    gradient: the output never requires grad.
+
+    Departure from the reference: its class has no ``DOWNSAMPLING`` attribute and no ``getDimOutput()``, so its own train.py and
+    FeatureModule fail on it; this one carries ``DOWNSAMPLING = 160`` (the hop) and ``getDimOutput()``, as LFBEnconder does.
+
+    ``topPerRow`` selects the scope of the maximum the dB floor hangs on: False (the default, the reference's behaviour: torchaudio
+    packs an (N, M, F) input as one item, so a quiet row is floored by a loud row of the same batch) or True (each row by its own
+    maximum: what calls on one row at a time give; harness.build_feature sets it around its batched call).
+
+    CUDA fp32 input with ``hip`` set and a shape ``ops.mfcc_supported`` takes runs ops.mfcc (HIP, csrc/mfcc.hip: the frames, the
+    spectrum and the power never reach memory).  Like LFBEnconder this module has a COMPLETE torch path -- the formula above on
+    torch.stft and two matmuls, from float64 copies of the tables -- which serves every other dtype and the CPU, and
+    ``hip=False`` selects it on the GPU too."""
+
+    def __init__(self, dimEncoded, hip=True):
+        super().__init__()
+        self.dimEncoded = dimEncoded
+        basis, fb, dct = ops.mfcc_tables(dimEncoded)
+        self.MFCC = nn.Module()
+        self.MFCC.MelSpectrogram = nn.Module()
+        self.MFCC.MelSpectrogram.spectrogram = nn.Module()
+        self.MFCC.MelSpectrogram.mel_scale = nn.Module()
+        self.MFCC.MelSpectrogram.spectrogram.register_buffer("window", ops.mfcc_window().float())
+        self.MFCC.MelSpectrogram.mel_scale.register_buffer("fb", fb)
+        self.MFCC.register_buffer("dct_mat", dct)
+        self.register_buffer("basis", basis, persistent=False)
+        self._exact = ops.mfcc_tables64(dimEncoded)          # float64 on the CPU: what the torch path computes from
+        self._cast = {}
+        self.register_load_state_dict_post_hook(MFCCEncoder._after_load)
+        self.hip = bool(hip)
+        self.topPerRow = False
+        self.DOWNSAMPLING = 160
+
+    def _buffers3(self):
+        return self.MFCC.MelSpectrogram.spectrogram.window, self.MFCC.MelSpectrogram.mel_scale.fb, self.MFCC.dct_mat
+
+    def _after_load(self, incompatible_keys):
+        """The loaded tables are the truth from now on: the torch path's copies and the kernel's basis follow them."""
+        with torch.no_grad():
+            self._exact = tuple(t.detach().to(device="cpu", dtype=torch.float64).clone() for t in self._buffers3())
+            self._cast = {}
+            self.basis.copy_(ops.mfcc_basis(self._exact[0]).to(self.basis))
+
+    def _tables(self, device, dtype):
+        key = (device, dtype)
+        if key not in self._cast:
+            self._cast = {key: tuple(t.to(device=device, dtype=dtype) for t in self._exact)}
+        return self._cast[key]
+
+    def getDimOutput(self):
+        return self.dimEncoded
+
+    def forward(self, x):
+        """(N, 1, L) or (N, L) -> (N, dimEncoded, (L - 1) // 160 + 1).  On the HIP path the result is the (N, D, F) view of a
+        contiguous (N, F, D) tensor, so CPCModel's permute(0, 2, 1) yields a contiguous z."""
+        N, L = x.size(0), x.size(-1)
+        if L < 161:
+            raise ValueError(f"MFCCEncoder: a window of {L} samples is shorter than the 161 a reflect padding of 160 needs")
+        x = x.detach().reshape(N, L)
+        window, fb, dct = self._buffers3()
+        if self.hip and x.is_cuda and x.dtype == torch.float32 and self.basis.is_cuda and self.basis.dtype == torch.float32 \
+                and fb.dtype == torch.float32 and dct.dtype == torch.float32 and ops.mfcc_supported(N, L, self.dimEncoded):
+            return ops.mfcc(x, self.basis, fb, dct, rowwise=self.topPerRow)
+        with torch.no_grad():
+            window, fb, dct = self._tables(x.device, x.dtype)
+            spec = torch.stft(x, 321, hop_length=160, win_length=321, window=window, center=True, pad_mode="reflect",
+                              normalized=False, onesided=True, return_complex=True)          # (N, 161, F)
+            power = spec.real ** 2 + spec.imag ** 2
+            db = 10.0 * torch.log10(torch.clamp(torch.matmul(power.transpose(1, 2), fb), min=1e-10))      # (N, F, M)
+            top = db.amax(dim=(1, 2), keepdim=True) if self.topPerRow else db.amax()
+            return torch.matmul(torch.maximum(db, top - 80.0), dct).permute(0, 2, 1)
+
+
 class NoAr(nn.Module):
     """cpc/model.py:207-213 (--arMode no_ar): the identity.  ``hip`` / ``reverse`` / ``keepHidden`` / ``hidden`` are there for the
     code that reads or sets them on any autoregressor (the fused step's check, the evaluation scripts' keepHidden)."""

@@ -1119,6 +1119,91 @@ class LfbFunction(torch.autograd.Function):
         return None, dW, db, None, None, None
 
 
+# ---- the MFCC encoder (csrc/mfcc.hip) ----------------------------------------------------------------------------------------
+_MFCC_FFT, _MFCC_HOP, _MFCC_BINS = 321, 160, 161
+
+
+def mfcc_frames(L):
+    """Frames of a window of L samples: centred frames of 321 samples at a hop of 160 over the reflect-padded window."""
+    return (L - 1) // _MFCC_HOP + 1
+
+
+def mfcc_mels(D):
+    """The reference's n_mels for n_mfcc = D (cpc/model.py:116)."""
+    return max(128, D)
+
+
+def mfcc_supported(N, L, D):
+    """The shapes cpc_mfcc_meldb / cpc_mfcc_dct take: N >= 1, L >= 161, 1 <= D <= 512, N F max(128, D) < 2^31."""
+    return N >= 1 and L >= _MFCC_BINS and 1 <= D <= 512 and N * mfcc_frames(L) * mfcc_mels(D) < (1 << 31)
+
+
+def mfcc_window():
+    """The periodic Hann window of 321 points in float64."""
+    return 0.5 - 0.5 * torch.cos(2 * torch.pi * torch.arange(_MFCC_FFT, dtype=torch.float64) / _MFCC_FFT)
+
+
+def mfcc_basis(window):
+    """The windowed DFT basis (321, 322) the kernel reads, fp32: columns 0..160 w[j] cos(2 pi j k / 321), columns 161..321
+    -w[j] sin(2 pi j k / 321); formed in float64 from ``window`` (321 values, any dtype) and rounded once."""
+    w = window.detach().reshape(-1).to(device="cpu", dtype=torch.float64)
+    jk = torch.arange(_MFCC_FFT, dtype=torch.int64)[:, None] * torch.arange(_MFCC_BINS, dtype=torch.int64)[None, :]
+    ang = 2 * torch.pi * (jk % _MFCC_FFT).double() / _MFCC_FFT          # (the angle reduced exactly, in integers)
+    return torch.cat([w[:, None] * torch.cos(ang), -w[:, None] * torch.sin(ang)], dim=1).float()
+
+
+def mfcc_tables64(D):
+    """(window (321), fb (161, M), dct (M, D)) in float64 on the CPU, M = max(128, D): the periodic Hann window, the HTK mel
+    filter bank over the grid linspace(0, 8000, 161) without area normalisation and the orthonormal DCT-II."""
+    M = mfcc_mels(D)
+    freqs = torch.linspace(0, 8000, _MFCC_BINS, dtype=torch.float64)
+    m_max = 2595.0 * torch.log10(torch.tensor(1.0 + 8000.0 / 700.0, dtype=torch.float64)).item()
+    f_pts = 700.0 * (10.0 ** (torch.linspace(0, m_max, M + 2, dtype=torch.float64) / 2595.0) - 1.0)
+    f_diff = f_pts[1:] - f_pts[:-1]
+    slopes = f_pts[None, :] - freqs[:, None]                              # (161, M + 2)
+    fb = torch.clamp(torch.minimum(-slopes[:, :-2] / f_diff[:-1], slopes[:, 2:] / f_diff[1:]), min=0.0)
+    m = torch.arange(M, dtype=torch.float64)[:, None]
+    d = torch.arange(D, dtype=torch.float64)[None, :]
+    dct = torch.cos(torch.pi / M * (m + 0.5) * d) * (2.0 / M) ** 0.5
+    dct[:, 0] *= 0.5 ** 0.5
+    return mfcc_window(), fb, dct
+
+
+def mfcc_tables(D):
+    """The three read-only tables of the MFCC encoder as fp32 CPU tensors, built in float64 and rounded once (include/cpc_hip.h):
+    basis (321, 322), fb (161, M) and dct (M, D), M = max(128, D)."""
+    window, fb, dct = mfcc_tables64(D)
+    return mfcc_basis(window), fb.float(), dct.float()
+
+
+def mfcc(x, basis, fb, dct, rowwise=False):
+    """x (N, 1, L) or (N, L) fp32 on the GPU and the tables of ``mfcc_tables`` on the same device -> the (N, D, F) VIEW of a
+    contiguous (N, F, D) tensor: MFCCEncoder's forward in two launches, cpc_mfcc_meldb and cpc_mfcc_dct.  ``rowwise``: the dB floor
+    hangs 80 dB below the maximum of each row instead of the whole call.  Nothing is differentiated: the result never requires
+    grad, and the unclamped dB tensor and the partial maxima are temporaries of the caching allocator on the current stream."""
+    _require_cuda(x, "mfcc")
+    lib = _lib.get()
+    N, L = x.shape[0], x.shape[-1]
+    M, D = dct.shape
+    if (x.numel() != N * L or tuple(basis.shape) != (_MFCC_FFT, 2 * _MFCC_BINS) or tuple(fb.shape) != (_MFCC_BINS, M)
+            or M != mfcc_mels(D)):
+        raise ValueError(f"mfcc: x {tuple(x.shape)}, basis {tuple(basis.shape)}, fb {tuple(fb.shape)}, dct {tuple(dct.shape)}")
+    if not mfcc_supported(N, L, D):
+        raise NotImplementedError(f"cpc_audio_amd.mfcc: unsupported shape N={N} L={L} D={D} (ops.mfcc_supported)")
+    for t in (basis, fb, dct):
+        _require_cuda(t, "mfcc")
+    x = x.detach().contiguous()
+    basis, fb, dct = basis.detach().contiguous(), fb.detach().contiguous(), dct.detach().contiguous()
+    with torch.cuda.device(x.device):
+        F, M_, ws_bytes = _layout("mfcc_layout", lib.cpc_mfcc_layout, 3, N, L, D)
+        db = torch.empty(N, F, M, device=x.device, dtype=torch.float32)
+        ws = torch.empty(ws_bytes // 4, device=x.device, dtype=torch.float32)
+        y = torch.empty(N, F, D, device=x.device, dtype=torch.float32)
+        lib.check(lib.cpc_mfcc_meldb(_p(x), _p(basis), _p(fb), _p(db), _p(ws), N, L, D, _stream()), "mfcc_meldb")
+        lib.check(lib.cpc_mfcc_dct(_p(db), _p(ws), _p(dct), _p(y), N, F, D, int(bool(rowwise)), _stream()), "mfcc_dct")
+    return y.permute(0, 2, 1)
+
+
 # ---- the frozen linear-separability step in one C call (csrc/probe.hip) ------------------------------------------------
 _probe_workspaces = {}
 

@@ -7,23 +7,30 @@ import torch
 
 from .criterion import CPCUnsupersivedCriterion
 from .dist import FlatGradAllReduce
-from .model import CPCAR, CPCEncoder, CPCModel, LFBEnconder, NoAr
+from .model import CPCAR, CPCEncoder, CPCModel, LFBEnconder, MFCCEncoder, NoAr
 from .optim import Adam
 
 
 def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False, reverse=False, arMode="GRU",
-                sizeWindow=20480, abspos=False, transformerDropout=0.1, lstmKernel=False, encoder_type="cpc", rnnKernel=False):
+                sizeWindow=20480, abspos=False, transformerDropout=0.1, lstmKernel=False, encoder_type="cpc", rnnKernel=False,
+                mfccKernel=False):
     """cpc/feature_loader.py:124-153 (getEncoder / getAR) + cpc/train.py:311.  arMode 'GRU' (north star) or
     'transformer' (BASELINE.json config 4: buildTransformerAR(hiddenEncoder, 1, sizeWindow // 160, abspos)); 'LSTM' /
     'RNN' as the reference (lstmKernel / rnnKernel: the LSTM / the RNN on the HIP kernels, CPCAR); 'no_ar': the identity, and the context width is
-    the encoder's (cpc/train.py:486).  encoder_type 'cpc' or 'lfb' (learned filter banks, LFBEnconder); 'mfcc' needs
-    torchaudio and is not built here."""
-    if encoder_type == "mfcc":
+    the encoder's (cpc/train.py:486).  encoder_type 'cpc' or 'lfb' (learned filter banks, LFBEnconder); 'mfcc' with
+    mfccKernel=True (not in the reference's signature; default off, as lstmKernel / rnnKernel) builds MFCCEncoder, this package's
+    restatement of torchaudio's MFCC on HIP kernels (hiddenEncoder coefficients); without the keyword 'mfcc' raises, since the
+    reference's class is torchaudio.transforms.MFCC and torchaudio is not a dependency."""
+    if encoder_type == "mfcc" and not mfccKernel:
         raise NotImplementedError("encoder_type 'mfcc' is torchaudio.transforms.MFCC in the reference; torchaudio is not a "
-                                  "dependency of this package and no MFCC encoder is built here")
-    if encoder_type not in ("cpc", "lfb"):
+                                  "dependency of this package.  Pass mfccKernel=True for MFCCEncoder, the package's own "
+                                  "restatement of that formula on HIP kernels")
+    if encoder_type not in ("cpc", "lfb", "mfcc"):
         raise ValueError(f"encoder_type must be 'cpc', 'lfb' or 'mfcc', got {encoder_type!r}")
-    enc = LFBEnconder(hiddenEncoder) if encoder_type == "lfb" else CPCEncoder(hiddenEncoder, "layerNorm")
+    if encoder_type == "mfcc":
+        enc = MFCCEncoder(hiddenEncoder)
+    else:
+        enc = LFBEnconder(hiddenEncoder) if encoder_type == "lfb" else CPCEncoder(hiddenEncoder, "layerNorm")
     if arMode == "no_ar":
         ar = NoAr()
     elif arMode == "transformer":

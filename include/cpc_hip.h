@@ -482,6 +482,30 @@ int cpc_lfb_lognorm_forward(const float* s, float* y, float* stats, int N, int F
 int cpc_lfb_lognorm_backward(const float* s, const float* stats, const float* dy, float* ds, int N, int F, int D, int normalise,
                              void* stream);
 
+/* ------------------------------------------------------- MFCC encoder (MFCCEncoder) ----
+ * cpc/model.py:108-122 (csrc/mfcc.hip): torchaudio.transforms.MFCC(n_mfcc = D, melkwargs = {n_mels: M, n_fft: 321}) with
+ * M = max(128, D) and torchaudio's documented defaults, restated (not compared with an installed torchaudio).  x (N, L) mono
+ * waveform; the three tables are fp32, read only and built by the caller (ops.mfcc_tables):
+ *   basis (321, 322)   basis[j][k] = w[j] cos(2 pi j k / 321), basis[j][161 + k] = -w[j] sin(2 pi j k / 321), k = 0 .. 160,
+ *                      w the periodic Hann window of 321 points
+ *   fb    (161, M)     the HTK mel filter bank over the grid linspace(0, 8000, 161), no area normalisation
+ *   dct   (M, D)       dct[m][d] = cos(pi / M (m + 0.5) d) sqrt(2 / M), column 0 times 1 / sqrt(2)
+ *   frame f, tap j     xf[j] = x[n, r(160 f - 160 + j)], r reflecting at both ends without repeating the edge sample,
+ *                      F = (L - 1) / 160 + 1 frames
+ *   p[n,f,k]  = (sum_j xf[j] basis[j][k])^2 + (sum_j xf[j] basis[j][161 + k])^2      (never stored)
+ *   db[n,f,m] = 10 log10(max(sum_k fb[k][m] p[n,f,k], 1e-10))
+ *   y[n,f,d]  = sum_m dct[m][d] max(db[n,f,m], top - 80),   top = max db over the whole call (rowwise = 1: over row n)
+ * cpc_mfcc_meldb writes db channels-last (N, F, M) and one partial maximum per workgroup into ws, in one launch: the three
+ * products run on exact-f32 MFMAs, the frames, the spectrum and the power stay in LDS and registers.  cpc_mfcc_dct reduces the
+ * partial maxima (a maximum: the same bits in any order, no atomics), clamps and writes y channels-last (N, F, D), one launch.
+ * cpc_mfcc_layout: sizes[0] = F, sizes[1] = M, sizes[2] = bytes of ws (N ceil(F / 32) floats).
+ * CPC_ERR_SHAPE for N < 1, L < 161 (cpc_mfcc_dct: F < 2), D < 1, D > 512 or N F max(M, D) >= 2^31; CPC_ERR_ARG for a NULL
+ * pointer or rowwise outside {0, 1}.  Arguments are checked before any launch; nothing is allocated, copied to the host or
+ * waited for. */
+int cpc_mfcc_layout(int N, int L, int D, long* sizes);
+int cpc_mfcc_meldb(const float* x, const float* basis, const float* fb, float* db, void* ws, int N, int L, int D, void* stream);
+int cpc_mfcc_dct(const float* db, const void* ws, const float* dct, float* y, int N, int F, int D, int rowwise, void* stream);
+
 /* ------------------------------------------------------- feed-forward prediction networks ----
  * --rnnMode ffd / conv4 / conv8 / conv12 of cpc/criterion/criterion.py:11-41,69-81 on the equalized layers of
  * custom_layers.py (csrc/pred_conv.hip): G heads of a causal convolution over the time axis, 256 -> 256 channels, ks taps,
