@@ -95,6 +95,10 @@ SIGNATURES = {
     "cpc_gemm_tn": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
     "cpc_nce_scores_forward": (_I, [_P] * 7 + [_I, _I, _I, _I, _P]),
     "cpc_nce_scores_backward": (_I, [_P] * 10 + [_I, _I, _I, _I, _P]),
+    "cpc_nce_wide_padded_width": (_I, [_I]),
+    "cpc_nce_wide_layout": (_I, [_I, _I, _I, _I, _I, _P]),
+    "cpc_nce_wide_forward": (_I, [_P] * 7 + [_I, _I, _I, _I, _I, _P]),
+    "cpc_nce_wide_backward": (_I, [_P] * 10 + [_I, _I, _I, _I, _I, _P]),
     "cpc_transformer_layout": (_I, [_I, _I, _P]),
     "cpc_transformer_hidden": (_I, [_P, _P, _I, _I, _P]),
     "cpc_transformer_layer_forward": (_I, [_P] * 5 + [_I, _I, _P]),

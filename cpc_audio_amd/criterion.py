@@ -12,7 +12,8 @@ import torch.nn as nn
 
 import torch.nn.functional as F
 
-from .ops import ClassifierXentFunction, CtcXentFunction, InfoNCEFunction, InfoNCEScoresFunction, prepare_negatives
+from .ops import (NCE_WIDE_MAX, ClassifierXentFunction, CtcXentFunction, InfoNCEFunction, InfoNCEScoresFunction,
+                  nce_wide_scores, prepare_negatives)
 
 _HEAD_TILE = 16          # prediction heads per call of the score kernels (a wavefront's MFMA tile; ops.head_group walks more)
 
@@ -147,8 +148,16 @@ class PredictionNetwork(nn.Module):
         # last_path names what the last call took
         self.hipPredictors = bool(hipPredictors)
         self.last_path = None
-        if dimOutputAR != 256 or dimOutputEncoder != 256:
-            raise NotImplementedError("the HIP criterion is built for hiddenGar == hiddenEncoder == 256")
+        if dimOutputAR < 1 or dimOutputEncoder < 1:
+            raise ValueError("PredictionNetwork: dimOutputAR and dimOutputEncoder must be positive")
+        if dimOutputEncoder > NCE_WIDE_MAX:
+            raise NotImplementedError(f"the HIP score kernels take hiddenEncoder up to {NCE_WIDE_MAX} (eight 64-channel blocks per "
+                                      f"wavefront), got {dimOutputEncoder}")
+        # 256 / 256 (north-star configuration): the linear heads fused into the criterion kernels of csrc/nce.hip.  Any other pair
+        # of widths: the predictions are formed as a tensor (scores_apart) and scored by the width-parametric kernels of
+        # csrc/nce_wide.hip (ops.nce_wide_scores)
+        self.wide = dimOutputAR != 256 or dimOutputEncoder != 256
+        self.dimOutputEncoder = dimOutputEncoder
         # (any number of prediction steps: the score tiles hold 16 heads per wavefront, a larger criterion is walked in groups of
         # 16 -- CPCUnsupersivedCriterion._forward_in_head_groups)
         self.predictors = nn.ModuleList()
@@ -169,18 +178,27 @@ class PredictionNetwork(nn.Module):
                 self.predictors.append(_TORCH_PREDICTORS[rnnMode](dimOutputAR, dimOutputEncoder))
             else:
                 self.predictors.append(nn.Linear(dimOutputAR, dimOutputEncoder, bias=False))
+                if dimOutputEncoder > dimOutputAR:
+                    # criterion.py:92-95: a head wider than the context starts as N(0, 1) on its first dimOutputAR output rows
+                    # and RESIDUAL_STD * N(0, 1) on the others
+                    residual = dimOutputEncoder - dimOutputAR
+                    with torch.no_grad():
+                        self.predictors[-1].weight.copy_(torch.cat([torch.randn(dimOutputAR, dimOutputAR),
+                                                                    self.RESIDUAL_STD * torch.randn(residual, dimOutputAR)], dim=0))
 
     @property
     def scores_apart(self):
         """True where the predictions exist as a tensor between the prediction networks and the scores (transformer predictors;
-        any predictor with the reference's dropout active): InfoNCEScoresFunction instead of the fused InfoNCEFunction."""
-        return (self.rnnMode == "transformer" or self.rnnMode in _TORCH_PREDICTORS
+        any predictor with the reference's dropout active; any widths other than 256 / 256): InfoNCEScoresFunction -- or, at
+        those other widths, ops.nce_wide_scores -- instead of the fused InfoNCEFunction."""
+        return (self.wide or self.rnnMode == "transformer" or self.rnnMode in _TORCH_PREDICTORS
                 or (self.dropout is not None and self.training))
 
     group_predictors = True      # False: the transformer predictors run head by head (the path a mixed set falls back to; tests)
 
     def predictions(self, c):
-        """c (B,W,256) -> (B,W,K*256): head k at columns k*256.. (the layout the score kernels read).  K one-layer transformer
+        """c (B,W,dimOutputAR) -> (B,W,K*dimOutputEncoder): head k at columns k*dimOutputEncoder.. (the layout the score kernels
+        read; 256 / 256 in the north-star configuration).  K one-layer transformer
         predictors (the only kind buildTransformerAR(.., 1, .., False) builds) run in lock-step, one launch per kernel for all
         of them (ops.TransformerGroupFunction); the K linear heads as one GEMM on the stacked weight; anything else head by head.
         The reference's dropout (criterion.py:113-114: per head, independent elementwise masks) is one dropout of the whole tensor."""
@@ -332,12 +350,18 @@ class CPCUnsupersivedCriterion(BaseCriterion):
                  hipPredictors=False):  # ffd / conv4 / conv8 / conv12 / LSTM / RNN predictors on HIP kernels (PredictionNetwork)
         super().__init__()
         if speakerEmbedding > 0:
-            raise NotImplementedError("speakerEmbedding is deprecated in the reference "
-                                      "(cpc_default_config.py:69-71) and not implemented here")
-        self.speakerEmb = None
+            # criterion.py:154-160, 238-241: a learned embedding of the speaker label widens the context the heads read
+            if nSpeakers < 1:
+                raise ValueError("speakerEmbedding needs nSpeakers >= 1")
+            self.speakerEmb = nn.Embedding(nSpeakers, speakerEmbedding)
+            dimOutputAR += speakerEmbedding
+        else:
+            self.speakerEmb = None
         self.wPrediction = PredictionNetwork(nPredicts, dimOutputAR, dimOutputEncoder, rnnMode=rnnMode,
                                              dropout=dropout, sizeInputSeq=sizeInputSeq - nPredicts,
                                              transformerDropout=transformerDropout, hipPredictors=hipPredictors)
+        if self.speakerEmb is not None:
+            self.wPrediction.wide = True          # (even at 256 + E -> 256 ... or 256 -> 256 heads: the context is formed here)
         self.nPredicts = nPredicts
         self.negativeSamplingExt = negativeSamplingExt
         # (any number: the kernels walk candidates in 16-wide tiles and mask the padding of the last one, ops.prepare_negatives)
@@ -403,8 +427,14 @@ class CPCUnsupersivedCriterion(BaseCriterion):
         batchSize, seqSize, _ = cFeature.size()
         windowSize = seqSize - self.nPredicts
         from . import ops
+        if self.wPrediction.wide:
+            ops._require_cuda(cFeature, "CPCUnsupersivedCriterion")
+            ops._require_cuda(encodedData, "CPCUnsupersivedCriterion")
+            if encodedData.shape[2] != self.wPrediction.dimOutputEncoder:
+                raise ValueError(f"CPCUnsupersivedCriterion: encodedData has {encodedData.shape[2]} channels, the heads predict "
+                                 f"{self.wPrediction.dimOutputEncoder}")
         if self.nPredicts > _HEAD_TILE:
-            return self._forward_in_head_groups(cFeature, encodedData, negatives)
+            return self._forward_in_head_groups(cFeature, encodedData, negatives, label)
         step = ops.current()
         prepared, saved = (step.prepared if step is not None else None), None
         if step is not None:
@@ -445,8 +475,11 @@ class CPCUnsupersivedCriterion(BaseCriterion):
             ext, perm, row_ptr = prepare_negatives(negatives[0], negatives[1], batchSize, seqSize, self.nPredicts,
                                                    self.negativeSamplingExt)
         if self.wPrediction.scores_apart:
-            pred = self.wPrediction.predictions(cFeature[:, :windowSize].contiguous())
-            losses, acc = InfoNCEScoresFunction.apply(pred, encodedData, ext, perm, row_ptr, self.negativeSamplingExt)
+            pred = self.wPrediction.predictions(self._context(cFeature, windowSize, label))
+            if self.wPrediction.wide:
+                losses, acc = nce_wide_scores(pred, encodedData, ext, perm, row_ptr, self.negativeSamplingExt)
+            else:
+                losses, acc = InfoNCEScoresFunction.apply(pred, encodedData, ext, perm, row_ptr, self.negativeSamplingExt)
         else:
             heads = [p.weight for p in self.wPrediction.predictors]
             # dz may be filled late (on the side stream) only if nobody outside this package can read it first: not in
@@ -456,7 +489,18 @@ class CPCUnsupersivedCriterion(BaseCriterion):
                                                 row_ptr, heads, defer, saved, self.negativeSamplingExt)
         return losses.view(1, -1), acc.view(1, -1)
 
-    def _forward_in_head_groups(self, cFeature, encodedData, negatives):
+    def _context(self, cFeature, windowSize, label):
+        """The first W steps of the context as the prediction networks read them: with a speaker embedding
+        (criterion.py:238-241) the embedded label of the sequence is appended to every step."""
+        c = cFeature[:, :windowSize].contiguous()
+        if self.speakerEmb is None:
+            return c
+        if label is None:
+            raise ValueError("CPCUnsupersivedCriterion: speakerEmbedding needs the speaker labels")
+        l_ = label.view(c.shape[0], 1).expand(c.shape[0], windowSize)
+        return torch.cat([c, self.speakerEmb(l_)], dim=2)
+
+    def _forward_in_head_groups(self, cFeature, encodedData, negatives, label=None):
         """nPredicts > 16 (no BASELINE config; the reference takes any): the same kernels on 16 heads at a time
         (ops.head_group -- every group sees the W = S - nPredicts windows of the whole criterion and the same negatives, head
         k's positive is z[t + k + 1]); the per-head losses and accuracies are independent, autograd adds the groups' dc / dz.
@@ -467,13 +511,16 @@ class CPCUnsupersivedCriterion(BaseCriterion):
         if negatives is None:
             negatives = self.drawNegatives(B, S, W, cFeature.device)
         wp = self.wPrediction
-        pred = wp.predictions(cFeature[:, :W].contiguous()) if wp.scores_apart else None
+        pred = wp.predictions(self._context(cFeature, W, label)) if wp.scores_apart else None
+        C = wp.dimOutputEncoder
         wall = None if wp.scores_apart else wp.stacked_weight()
         losses, accs = [], []
         for k0 in range(0, K, _HEAD_TILE):
             kg = min(_HEAD_TILE, K - k0)
             ext, perm, row_ptr = prepare_negatives(negatives[0], negatives[1], B, S, kg, N, group=(k0, K))
-            if wp.scores_apart:
+            if wp.wide:
+                l, a = nce_wide_scores(pred[:, :, k0 * C:(k0 + kg) * C], encodedData, ext, perm, row_ptr, N, (k0, K))
+            elif wp.scores_apart:
                 l, a = InfoNCEScoresFunction.apply(pred[:, :, k0 * 256:(k0 + kg) * 256], encodedData, ext, perm, row_ptr, N,
                                                    (k0, K))
             else:

@@ -232,6 +232,9 @@ int ctc_error_flag_fetch(int clear, unsigned* out);        // ctc_loss.hip: bit 
 int seqnorm_error_flag_fetch(int clear, unsigned* out);    // seqnorm.hip: CPC_DEVERR_LENGTH_RANGE
 int rnn_error_flag_fetch(int clear, unsigned* out);        // rnn.hip: CPC_DEVERR_RNN_POLL_TIMEOUT
 
+// nce.hip: the calling thread's head group as cpc_nce_head_group set it ((0, 0): none)
+void nce_head_group_get(int* k0, int* k_total);
+
 static inline long align64l(long v) { return (v + 63) & ~63L; }
 
 }  // namespace cpc

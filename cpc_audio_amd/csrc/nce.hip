@@ -1623,6 +1623,9 @@ static int nce_scores_backward(const NceLayout& n, const float* z, const int* ex
     return 0;
 }
 
+// the calling thread's head group (cpc_nce_head_group), for the score kernels of other translation units (nce_wide.hip)
+void nce_head_group_get(int* k0, int* k_total) { *k0 = g_head_off; *k_total = g_head_total; }
+
 // bit 1 of cpc_device_error_flags(): cpc_nce_prepare saw an out-of-range negative index
 int nce_error_flag_fetch(int clear, unsigned* out) { return device_flag_fetch(HIP_SYMBOL(g_nce_bad_index), clear, out); }
 

@@ -1524,6 +1524,91 @@ class InfoNCEScoresFunction(torch.autograd.Function):
         return dpred, dz, None, None, None, None, None
 
 
+NCE_WIDE_MAX = 512        # widest encoder the width-parametric score kernels take (csrc/nce_wide.hip: eight 64-float blocks)
+
+
+def nce_wide_supported(C):
+    """Do the width-parametric score kernels (cpc_nce_wide_*) take an encoder of width C?  1 <= C <= 512."""
+    return 1 <= int(C) <= NCE_WIDE_MAX
+
+
+def nce_wide_padded_width(C):
+    """C rounded up to the kernels' 64-float channel block (cpc_nce_wide_padded_width)."""
+    if not nce_wide_supported(C):
+        raise NotImplementedError(f"the HIP score kernels take encoder widths 1 .. {NCE_WIDE_MAX}, got {C}")
+    return (int(C) + 63) // 64 * 64
+
+
+class InfoNCEWideScoresFunction(torch.autograd.Function):
+    """InfoNCEScoresFunction at any encoder width C <= 512: pred (B,W,K*Cp) from any prediction network, z (B,S,Cp) with
+    Cp = nce_wide_padded_width(C) and ZERO columns C .. Cp-1 of every head / row, ext, perm, row_ptr -> losses (K), acc (K)
+    (cpc_nce_wide_{forward,backward}: exact-f32 MFMAs, dz through per-candidate rows and the destination-sorted gather).  The
+    gradients have the inputs' padded shapes and are exactly zero in the padding columns; nce_wide_scores pads for the caller."""
+
+    @staticmethod
+    def forward(ctx, pred, z, ext, perm, row_ptr, C, n_valid=None, group=None):
+        _require_cuda(pred, "InfoNCEWideScoresFunction")
+        _require_cuda(z, "InfoNCEWideScoresFunction")
+        lib = _lib.get()
+        B, S, Cp = z.shape
+        W, N = ext.shape[1], ext.shape[2]
+        C = int(C)
+        if n_valid is not None:                       # (ext rows padded to the 16-wide tile: prepare_negatives)
+            if int(lib.cpc_nce_padded_negatives(int(n_valid))) != N:
+                raise ValueError("InfoNCEWideScoresFunction: ext is not padded for n_valid negatives")
+            N = int(n_valid)
+        if Cp != nce_wide_padded_width(C):
+            raise ValueError(f"InfoNCEWideScoresFunction: z must be padded to {nce_wide_padded_width(C)} channels for C = {C}")
+        K = S - W if group is None else pred.shape[2] // Cp          # (group = (k0, k_total): pred holds heads k0 .. k0+K-1)
+        if (pred.shape != (B, W, K * Cp) or ext.dtype != torch.int32 or (group is not None and W != S - group[1])):
+            raise ValueError("InfoNCEWideScoresFunction: inconsistent shapes")
+        pred, z, ext = pred.contiguous(), z.contiguous(), ext.contiguous()
+        with torch.cuda.device(z.device), head_group(lib, group):
+            sizes = _layout(f"nce_wide_layout{group or ''}", lib.cpc_nce_wide_layout, 5, B, S, K, N, C)
+            saved = torch.empty(sizes[0], device=z.device, dtype=torch.float32)
+            scratch = torch.empty(sizes[1], device=z.device, dtype=torch.float32)
+            losses = torch.empty(K, device=z.device, dtype=torch.float32)
+            acc = torch.empty(K, device=z.device, dtype=torch.float32)
+            lib.check(lib.cpc_nce_wide_forward(_p(pred), _p(z), _p(ext), _p(saved), _p(scratch), _p(losses), _p(acc),
+                                               B, S, K, N, C, _stream()), "nce_wide_forward")
+        ctx.save_for_backward(pred, z, ext, saved, perm, row_ptr)
+        ctx.dims = (B, S, K, N, C, sizes[2])
+        ctx.group = group
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(acc)
+        return losses, acc
+
+    @staticmethod
+    def backward(ctx, gloss, _gacc):
+        lib = _lib.get()
+        pred, z, ext, saved, perm, row_ptr = ctx.saved_tensors
+        B, S, K, N, C, nscr = ctx.dims
+        gloss = torch.zeros(K, device=z.device) if gloss is None else gloss.contiguous()
+        with torch.cuda.device(z.device), head_group(lib, ctx.group):
+            scratch = torch.empty(nscr, device=z.device, dtype=torch.float32)
+            dpred, dz = torch.empty_like(pred), torch.empty_like(z)
+            lib.check(lib.cpc_nce_wide_backward(_p(pred), _p(z), _p(ext), _p(perm), _p(row_ptr), _p(saved), _p(gloss),
+                                                _p(scratch), _p(dpred), _p(dz), B, S, K, N, C, _stream()),
+                      "nce_wide_backward")
+        return dpred, dz, None, None, None, None, None, None
+
+
+def nce_wide_scores(pred, z, ext, perm, row_ptr, n_valid=None, group=None):
+    """InfoNCEWideScoresFunction on unpadded tensors: pred (B,W,K*C), z (B,S,C) -> losses (K), acc (K).  The channel padding is
+    made here with differentiable torch ops, and only when C is not a multiple of 64 (otherwise nothing is copied)."""
+    _require_cuda(pred, "nce_wide_scores")
+    _require_cuda(z, "nce_wide_scores")
+    B, S, C = z.shape
+    Cp = nce_wide_padded_width(C)
+    if pred.dim() != 3 or pred.shape[2] % C != 0:
+        raise ValueError("nce_wide_scores: pred must be (B, W, K*C)")
+    if Cp != C:
+        Bp, W, KC = pred.shape
+        pred = torch.nn.functional.pad(pred.reshape(Bp, W, KC // C, C), (0, Cp - C)).reshape(Bp, W, KC // C * Cp)
+        z = torch.nn.functional.pad(z, (0, Cp - C))
+    return InfoNCEWideScoresFunction.apply(pred, z, ext, perm, row_ptr, C, n_valid, group)
+
+
 class TransformerGroupFunction(torch.autograd.Function):
     """x (B,S,256), dropout probability, seed, G + the 13 parameter kinds of G TransformerLayers, each stacked (G, ...)
     (Krelpos possibly None) -> (B,S,G*256), layer g at columns g*256..: the K transformer predictors of the criterion on the

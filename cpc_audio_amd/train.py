@@ -44,9 +44,10 @@ def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False
 
 def build_criterion(nPredicts=12, hiddenGar=256, hiddenEncoder=256, negativeSamplingExt=128,
                     sizeWindow=20480, downsampling=160, mode=None, rnnMode="linear", transformerDropout=0.1, dropout=False,
-                    hipPredictors=False):
+                    hipPredictors=False, speakerEmbedding=0, nSpeakers=0):
     return CPCUnsupersivedCriterion(nPredicts, hiddenGar, hiddenEncoder, negativeSamplingExt, mode=mode,
-                                    rnnMode=rnnMode, dropout=dropout, sizeInputSeq=sizeWindow // downsampling,
+                                    rnnMode=rnnMode, dropout=dropout, speakerEmbedding=speakerEmbedding, nSpeakers=nSpeakers,
+                                    sizeInputSeq=sizeWindow // downsampling,
                                     transformerDropout=transformerDropout, hipPredictors=hipPredictors)
 
 

@@ -803,6 +803,21 @@ int cpc_nce_scores_backward(const float* pred, const float* z, const int* ext, c
                             const int* row_ptr, const float* saved, const float* gloss, float* scratch,
                             float* dpred, float* dz, int B, int S, int K, int N, void* stream);
 
+/* The same scores at any encoder width 1 <= C <= 512 (cpc/criterion/criterion.py:89-95 takes any dimOutputEncoder; :116's mean is
+ * over C), on exact-f32 MFMAs (csrc/nce_wide.hip).  The kernels work on the padded width Cp = cpc_nce_wide_padded_width(C) = C
+ * rounded up to a multiple of 64 (0 for C < 1 or C > 512): pred is (B*W, K*Cp), z (B, S, Cp), columns C .. Cp-1 ZERO; dpred and dz
+ * have the same shapes and come out exactly zero there.  ext / perm / row_ptr are those of cpc_nce_prepare (they do not depend
+ * on the width); K <= 16 per call, more heads through cpc_nce_head_group; any N >= 1 (padded as cpc_nce_padded_negatives).
+ * sizes (floats): [0] saved, [1] forward scratch, [2] backward scratch (B*W*(Np+K)*Cp candidate rows: every offset is 64-bit),
+ * [3] offset of logits (B*W, K, Np+1) in saved, [4] of lse (B*W, K).  Every output is overwritten completely. */
+int cpc_nce_wide_padded_width(int C);
+int cpc_nce_wide_layout(int B, int S, int K, int N, int C, long* sizes);
+int cpc_nce_wide_forward(const float* pred, const float* z, const int* ext, float* saved, float* scratch,
+                         float* losses, float* acc, int B, int S, int K, int N, int C, void* stream);
+int cpc_nce_wide_backward(const float* pred, const float* z, const int* ext, const int* perm, const int* row_ptr,
+                          const float* saved, const float* gloss, float* scratch, float* dpred, float* dz,
+                          int B, int S, int K, int N, int C, void* stream);
+
 /* ---- the whole step ---------------------------------------------------------------------------------------------------
  * cpc/train.py:78-87 for the north-star configuration (CPCEncoder + 2-layer GRU CPCAR + K linear InfoNCE heads): model
  * forward, criterion forward, allLosses.sum().backward() -- every launch of the entry points above, issued from ONE call on
