@@ -127,6 +127,18 @@ SIGNATURES = {
     "cpc_rnn_layout": (_I, [_I, _I, _I, _I, _P]),
     "cpc_rnn_forward": (_I, [_P] * 7 + [_I, _I, _I, _I, _I, _P]),
     "cpc_rnn_backward": (_I, [_P] * 9 + [_I, _I, _I, _I, _I, _P]),
+    "cpc_gru_layout_in": (_I, [_I, _I, _I, _I, _P]),
+    "cpc_gru_forward_in": (_I, [_P] * 7 + [_I, _I, _I, _I, _P]),
+    "cpc_gru_backward_in": (_I, [_P] * 9 + [_I, _I, _I, _I, _P]),
+    "cpc_lstm_layout_in": (_I, [_I, _I, _I, _I, _P]),
+    "cpc_lstm_forward_in": (_I, [_P] * 9 + [_I, _I, _I, _I, _I, _P]),
+    "cpc_lstm_backward_in": (_I, [_P] * 10 + [_I, _I, _I, _I, _I, _P]),
+    "cpc_rnn_layout_in": (_I, [_I, _I, _I, _I, _P]),
+    "cpc_rnn_forward_in": (_I, [_P] * 7 + [_I, _I, _I, _I, _I, _P]),
+    "cpc_rnn_backward_in": (_I, [_P] * 9 + [_I, _I, _I, _I, _I, _P]),
+    "cpc_in_proj_scratch_floats": (_L, [_I, _I, _I]),
+    "cpc_in_proj_forward": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "cpc_in_proj_backward": (_I, [_P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "cpc_supervised_layout": (_I, [_I, _I, _I, _I, _P]),
     "cpc_classifier_forward": (_I, [_P, _L] + [_P] * 6 + [_I, _I, _P]),
     "cpc_classifier_backward": (_I, [_P, _L] + [_P] * 9 + [_I, _I, _P]),

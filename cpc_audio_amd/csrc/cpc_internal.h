@@ -91,6 +91,19 @@ int transpose(const float* in, float* out, int R, int Cn, hipStream_t st, int G 
 // n <= 4 matrices of one shape in one launch
 int transpose_batch(const float* const* in, float* const* out, int n, int R, int Cn, hipStream_t st);
 
+// ---- in_proj.hip: layer 0's input projection of the recurrent cells at an input width D in 1..kInProjMaxD other than 256
+// (exact-f32 MFMAs; x and dx rows ldx >= D floats apart, any 4-byte alignment; N % 128 == 0; out, dG and scratch 16-byte aligned)
+constexpr int kInProjMaxD = 512;
+bool in_proj_shape_ok(long M, int N, int D);
+long in_proj_w_floats(int N, int D);                 // scratch of the forward: the zero-padded weight copy
+long in_proj_scratch_floats(long M, int N, int D);   // scratch of the backward: that + the weight gradient's split partials
+// out[M,N] = x . W[N,D]^T + bias (bias may be NULL)
+int in_proj_forward(const float* x, long ldx, const float* W, const float* bias, float* scratch, float* out, int M, int N, int D,
+                    hipStream_t st);
+// dx[M,D] = dG[M,N] . W and dW[N,D] = dG^T . x (fixed-order split reduction); dx or dW may be NULL
+int in_proj_backward(const float* x, long ldx, const float* W, const float* dG, float* scratch, float* dx, float* dW, int M, int N,
+                     int D, hipStream_t st);
+
 // ---- gemm_dma.hip: plain GEMMs on the DMA-fed tile, operands in H2 storage (every stride in floats = H2 elements; bounds as
 // kAmaxSlots partial maxima; G problems per launch, problem g at + g * the *_gs strides)
 bool gemm_dma_wanted(int M, int G);

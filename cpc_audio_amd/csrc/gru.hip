@@ -1079,13 +1079,16 @@ struct GruLayout {
     long coef, xdh, frag_floats;             // two-layer path: 8 coefficient arrays, 3 hand-over buffers (fragment order: xdh[0], xdh[1], xdh1r)
     long sync_floats;                        // ... and, behind either set of hand-over buffers, four words per batch tile (on_one_xcd)
     long bwd_total;
+    long ipf, ipb;                           // D != 256: in_proj.hip's scratch behind the forward's / the backward's (the totals include it)
 };
 
 constexpr int kXdhBufs = 3;                  // hand-over buffers of the persistent backward: xdh[0], xdh[1], xdh1r
 constexpr int kCoefBufs = 8 + kXdhBufs;      // fragment-ordered arrays at the head of the `coef` buffer (cpc_gru_coef_floats)
 
-static bool gru_layout(int B, int S, int nl, GruLayout& g) {
+// D: the input width of layer 0 (cpc_gru_*_in); at 256 the layout is the one cpc_gru_layout has always reported
+static bool gru_layout(int B, int S, int nl, GruLayout& g, int D = kH) {
     if (B <= 0 || S <= 0 || nl <= 0 || nl > 8) return false;
+    if (D < 1 || D > kInProjMaxD || (D != kH && !in_proj_shape_ok((long)B * S, kG, D))) return false;
     const long bsh = align64l((long)B * S * kH);
     long o = 0;
     for (int l = 0; l < nl; ++l) {
@@ -1111,7 +1114,9 @@ static bool gru_layout(int B, int S, int nl, GruLayout& g) {
     g.DH = o; o += bsh;
     g.mid[0] = o; o += bsh;
     g.mid[1] = o; o += bsh;
-    g.part = o; o += align64l(std::max(tn_gemm_part_floats(B * S, kG, kH), tn_gemm_batch_part_floats(4, B * S, kG, kH)));
+    long part = std::max(tn_gemm_part_floats(B * S, kG, kH), tn_gemm_batch_part_floats(4, B * S, kG, kH));
+    if (D != kH) part = std::max(part, tn_gemm_batch_part_floats(3, B * S, kG, kH));     // (a batch of three may split finer)
+    g.part = o; o += align64l(part);
     g.tmp = o; o += 4 * align64l((long)kRowsSumGroups * kG);      // one per bias reduction of the batched sum
     g.whhT2 = o; o += (long)kH * kG;
     g.wihT2 = o; o += (long)kH * kG;
@@ -1122,6 +1127,11 @@ static bool gru_layout(int B, int S, int nl, GruLayout& g) {
     g.coef = o; o += 8 * g.frag_floats;
     g.xdh = o; o += kXdhBufs * g.frag_floats + g.sync_floats;
     g.bwd_total = o;
+    g.ipf = g.fwd_total; g.ipb = g.bwd_total;
+    if (D != kH) {
+        g.fwd_total += in_proj_w_floats(kG, D);
+        g.bwd_total += in_proj_scratch_floats((long)B * S, kG, D);
+    }
     return true;
 }
 
@@ -1306,7 +1316,7 @@ extern "C" int cpc_gru_forward(const float* x, const float* h0, const float* con
 // -- by the persistent forward's gate threads where that path runs, by gru_bwd_coef_kernel behind the forward otherwise --
 // and cpc_gru_backward_coef(..., coef_done = 1) only has the hand-over buffers and the weight transposes left to prepare.
 static int gru_forward_impl(const float* x, const float* h0, const float* const* params, float* saved, float* scratch, float* y,
-                            float* hN, float* coef, int B, int S, int nl, void* stream, bool xh_ready);
+                            float* hN, float* coef, int B, int S, int nl, void* stream, bool xh_ready, int D = kH);
 extern "C" int cpc_gru_forward_coef(const float* x, const float* h0, const float* const* params, float* saved,
                                     float* scratch, float* y, float* hN, float* coef, int B, int S, int nl, void* stream) {
     return gru_forward_impl(x, h0, params, saved, scratch, y, hN, coef, B, S, nl, stream, false);
@@ -1325,16 +1335,29 @@ extern "C" int cpc_gru_forward_coef_prepared(const float* x, const float* h0, co
                                              float* scratch, float* y, float* hN, float* coef, int B, int S, int nl, void* stream) {
     return gru_forward_impl(x, h0, params, saved, scratch, y, hN, coef, B, S, nl, stream, true);
 }
-static int gru_forward_impl(const float* x, const float* h0, const float* const* params, float* saved, float* scratch, float* y,
-                            float* hN, float* coef, int B, int S, int nl, void* stream, bool xh_ready) {
+// D: x is (B,S,D) and weight_ih_l0 (3H,D) (cpc_gru_forward_in); layer 0's input projection then runs in in_proj.hip
+extern "C" int cpc_gru_layout_in(int B, int S, int nl, int D, long* sizes) {
     GruLayout g;
-    CPC_RETURN_IF(!gru_layout(B, S, nl, g), CPC_ERR_SHAPE);
+    CPC_RETURN_IF(!gru_layout(B, S, nl, g, D), CPC_ERR_SHAPE);
+    CPC_RETURN_IF(!sizes, CPC_ERR_ARG);
+    sizes[0] = g.saved_total; sizes[1] = g.fwd_total; sizes[2] = g.bwd_total;
+    return 0;
+}
+extern "C" int cpc_gru_forward_in(const float* x, const float* h0, const float* const* params, float* saved, float* scratch,
+                                  float* y, float* hN, int B, int S, int nl, int D, void* stream) {
+    return gru_forward_impl(x, h0, params, saved, scratch, y, hN, nullptr, B, S, nl, stream, false, D);
+}
+static int gru_forward_impl(const float* x, const float* h0, const float* const* params, float* saved, float* scratch, float* y,
+                            float* hN, float* coef, int B, int S, int nl, void* stream, bool xh_ready, int D) {
+    GruLayout g;
+    CPC_RETURN_IF(!gru_layout(B, S, nl, g, D), CPC_ERR_SHAPE);
     CPC_RETURN_IF(!x || !params || !saved || !scratch || !y || !hN, CPC_ERR_ARG);
     hipStream_t st = (hipStream_t)stream;
     const float* in = x;
     float* gi = scratch + g.gi;
     if (nl == 2) {                                   // two-layer wavefront (see gru2_fwd_kernel)
-        int rc = nt_gemm(plain_rows(x, B * S, kH), params[0], kH, params[2], gi, kG, kG, kH, st);
+        int rc = D != kH ? in_proj_forward(x, D, params[0], params[2], scratch + g.ipf, gi, B * S, kG, D, st)
+                         : nt_gemm(plain_rows(x, B * S, kH), params[0], kH, params[2], gi, kG, kG, kH, st);
         if (rc) return rc;
         Gru2Fwd p;
         p.x_gi0 = gi;
@@ -1394,7 +1417,8 @@ static int gru_forward_impl(const float* x, const float* h0, const float* const*
     for (int l = 0; l < nl; ++l) {
         const float* wih = params[4 * l], *whh = params[4 * l + 1], *bih = params[4 * l + 2], *bhh = params[4 * l + 3];
         float* out = (l == nl - 1) ? y : saved + g.Y[l];
-        int rc = nt_gemm(plain_rows(in, B * S, kH), wih, kH, bih, gi, kG, kG, kH, st);
+        int rc = l == 0 && D != kH ? in_proj_forward(x, D, wih, bih, scratch + g.ipf, gi, B * S, kG, D, st)
+                                   : nt_gemm(plain_rows(in, B * S, kH), wih, kH, bih, gi, kG, kG, kH, st);
         if (rc) return rc;
         const float* h0l = h0 ? h0 + (long)l * B * kH : nullptr;
         const dim3 grid(kH / 16, cdiv(B, 16));
@@ -1477,18 +1501,33 @@ extern "C" int cpc_gru_backward_with_coef(const float* x, const float* h0, const
 // batched TN GEMM) and the four bias gradients -- on `wgrad_stream`, released by an event behind the recurrence; dx
 // (what the encoder's backward waits for) stays on `stream`.  NO join: the caller orders every consumer of `grads`
 // after `wgrad_stream`, and keeps `scratch` alive until then.  nl == 2 only; other depths run on `stream` alone.
+static int gru_backward_impl(const float* x, const float* h0, const float* const* params, const float* saved, const float* y,
+                             const float* dy, const float* coef, float* scratch, float* dx, float* const* grads, int B, int S,
+                             int nl, void* stream, void* wgrad_stream, int D);
 extern "C" int cpc_gru_backward_streams(const float* x, const float* h0, const float* const* params,
                                         const float* saved, const float* y, const float* dy, const float* coef,
                                         float* scratch, float* dx, float* const* grads, int B, int S, int nl,
                                         void* stream, void* wgrad_stream) {
+    return gru_backward_impl(x, h0, params, saved, y, dy, coef, scratch, dx, grads, B, S, nl, stream, wgrad_stream, kH);
+}
+// D: x, dx (B,S,D), weight_ih_l0 and its gradient (3H,D): no prepared coefficients, one stream
+extern "C" int cpc_gru_backward_in(const float* x, const float* h0, const float* const* params, const float* saved, const float* y,
+                                   const float* dy, float* scratch, float* dx, float* const* grads, int B, int S, int nl, int D,
+                                   void* stream) {
+    return gru_backward_impl(x, h0, params, saved, y, dy, nullptr, scratch, dx, grads, B, S, nl, stream, stream, D);
+}
+static int gru_backward_impl(const float* x, const float* h0, const float* const* params, const float* saved, const float* y,
+                             const float* dy, const float* coef, float* scratch, float* dx, float* const* grads, int B, int S,
+                             int nl, void* stream, void* wgrad_stream, int D) {
     GruLayout g;
-    CPC_RETURN_IF(!gru_layout(B, S, nl, g), CPC_ERR_SHAPE);
+    CPC_RETURN_IF(!gru_layout(B, S, nl, g, D), CPC_ERR_SHAPE);
     CPC_RETURN_IF(!x || !params || !saved || !scratch || !y || !dy || !dx || !grads, CPC_ERR_ARG);
     hipStream_t st = (hipStream_t)stream;
     hipStream_t wst = nl == 2 ? (hipStream_t)wgrad_stream : st;
     float* whhT = scratch + g.whhT, *wihT = scratch + g.wihT;
     float* dGi = scratch + g.dGi, *dGh = scratch + g.dGh, *DH = scratch + g.DH;
     const int M = B * S;
+    const bool narrow = D != kH;                     // layer 0 at another input width: its three products in in_proj.hip
     if (nl == 2) {                                   // two-layer wavefront (see gru2_bwd_kernel)
         // (the transposed weights come with `coef` when the caller prepared it, cpc_gru_backward_coef)
         float* cwT = coef ? const_cast<float*>(coef) + kCoefBufs * g.frag_floats + g.sync_floats : nullptr;
@@ -1507,7 +1546,8 @@ extern "C" int cpc_gru_backward_streams(const float* x, const float* h0, const f
         if (!coef) {   // (3H,H) -> (H,3H), the four weight matrices in one launch
             const float* tin[4] = {params[1], params[0], params[5], params[4]};
             float* tout[4] = {whhT_[0], wihT_[0], whhT_[1], wihT_[1]};
-            rc = transpose_batch(tin, tout, 4, kG, kH, st);
+            if (narrow) { tin[1] = tin[3]; tout[1] = tout[3]; }      // (W_ih0 is (3H,D): in_proj.hip reads it as it lies)
+            rc = transpose_batch(tin, tout, narrow ? 3 : 4, kG, kH, st);
             if (rc) return rc;
         }
         for (int l = 0; l < 2; ++l) {
@@ -1552,7 +1592,8 @@ extern "C" int cpc_gru_backward_streams(const float* x, const float* h0, const f
         SplitK sk;                       // N = 256: too few tiles for the chip; the partial buffer of the weight gradients is free
         sk.part = scratch + g.part;      // until they start (behind this GEMM, on either stream)
         sk.floats = std::max(tn_gemm_part_floats(B * S, kG, kH), tn_gemm_batch_part_floats(4, B * S, kG, kH));
-        rc = nt_gemm(plain_rows(dGi_[0], M, kG), wihT_[0], kG, nullptr, dx, kH, kH, kG, st, 0, 0, GemmBounds(), GemmGroup(), sk);
+        rc = narrow ? in_proj_backward(x, D, params[0], dGi_[0], scratch + g.ipb, dx, nullptr, M, kG, D, st)
+                    : nt_gemm(plain_rows(dGi_[0], M, kG), wihT_[0], kG, nullptr, dx, kH, kH, kG, st, 0, 0, GemmBounds(), GemmGroup(), sk);
         if (rc) return rc;
         if (wst != st) {
             hipEvent_t* ev = stream_events(st);
@@ -1579,7 +1620,13 @@ extern "C" int cpc_gru_backward_streams(const float* x, const float* h0, const f
                 bm[2 * l + 1] = hm;
                 Cq[2 * l + 1] = grads[4 * l + 1];
             }
-            rc = tn_gemm_batch(4, am, kG, bm, kH, scratch + g.part, Cq, 0, wst);
+            if (narrow) {                              // dW_ih0 is (3H,D): it leaves the batch, the other three stay in it
+                rc = in_proj_backward(x, D, params[0], dGi_[0], scratch + g.ipb, nullptr, grads[0], M, kG, D, wst);
+                if (rc) return rc;
+                rc = tn_gemm_batch(3, am + 1, kG, bm + 1, kH, scratch + g.part, Cq + 1, 0, wst);
+            } else {
+                rc = tn_gemm_batch(4, am, kG, bm, kH, scratch + g.part, Cq, 0, wst);
+            }
             if (rc) return rc;
         }
         for (int l = 0; l < 2; ++l) {
@@ -1603,7 +1650,7 @@ extern "C" int cpc_gru_backward_streams(const float* x, const float* h0, const f
         float* dXl = l == 0 ? dx : scratch + g.mid[l & 1];
         int rc = transpose(whh, whhT, kG, kH, st);       // (3H,H) -> (H,3H)
         if (rc) return rc;
-        rc = transpose(wih, wihT, kG, kH, st);
+        rc = l == 0 && narrow ? 0 : transpose(wih, wihT, kG, kH, st);
         if (rc) return rc;
         const dim3 grid(kH / 16, cdiv(B, 16));
         for (int t = S - 1; t >= 0; --t)
@@ -1613,7 +1660,8 @@ extern "C" int cpc_gru_backward_streams(const float* x, const float* h0, const f
         CPC_LAUNCH_CHECK();
         // weight / bias gradients over all B*S rows
         const RowMap gim = plain_rows(dGi, M, kG), ghm = plain_rows(dGh, M, kG);
-        rc = tn_gemm(gim, kG, plain_rows(in, M, kH), kH, scratch + g.part, grads[4 * l], 0, st);
+        rc = l == 0 && narrow ? in_proj_backward(x, D, wih, dGi, scratch + g.ipb, nullptr, grads[0], M, kG, D, st)
+                              : tn_gemm(gim, kG, plain_rows(in, M, kH), kH, scratch + g.part, grads[4 * l], 0, st);
         if (rc) return rc;
         // h_{t-1} rows: y[b, t-1] (zero row at t = 0; the h0 term is added below)
         RowMap hm;
@@ -1633,7 +1681,8 @@ extern "C" int cpc_gru_backward_streams(const float* x, const float* h0, const f
         rc = rows_sum(dGh, M, kG, scratch + g.tmp, grads[4 * l + 3], st);
         if (rc) return rc;
         // dX = dGi . W_ih   (as NT against W_ih^T)
-        rc = nt_gemm(gim, wihT, kG, nullptr, dXl, kH, kH, kG, st);
+        rc = l == 0 && narrow ? in_proj_backward(x, D, wih, dGi, scratch + g.ipb, dx, nullptr, M, kG, D, st)
+                              : nt_gemm(gim, wihT, kG, nullptr, dXl, kH, kH, kG, st);
         if (rc) return rc;
         dYl = dXl;
     }

@@ -308,10 +308,13 @@ struct LstmLayout {
     long saved_total;
     long gx, fwd_total;
     long whhT, wihT, dG, DC, mid[2], part, tmp, bwd_total;
+    long ipf, ipb;        // D != 256: in_proj.hip's scratch behind the forward's / the backward's (the totals include it)
 };
 
-static bool lstm_layout(int B, int S, int nl, LstmLayout& g) {
+// D: the input width of layer 0 (cpc_lstm_*_in); at 256 the layout is the one cpc_lstm_layout has always reported
+static bool lstm_layout(int B, int S, int nl, LstmLayout& g, int D = kLH) {
     if (B <= 0 || S <= 0 || nl <= 0 || nl > 8) return false;
+    if (D < 1 || D > kInProjMaxD) return false;
     if ((long)B * S > (1L << 21)) return false;          // B*S*4H floats stay below 2^31 (int GEMM rows and offsets)
     const long bsh = align64l((long)B * S * kLH), bsg = align64l((long)B * S * kLG);
     long o = 0;
@@ -334,6 +337,11 @@ static bool lstm_layout(int B, int S, int nl, LstmLayout& g) {
     g.part = o; o += align64l(tn_gemm_part_floats(B * S, kLG, kLH));
     g.tmp = o; o += align64l((long)kRowsSumGroups * kLG);
     g.bwd_total = o;
+    g.ipf = g.fwd_total; g.ipb = g.bwd_total;
+    if (D != kLH) {
+        g.fwd_total += in_proj_w_floats(kLG, D);
+        g.bwd_total += in_proj_scratch_floats((long)B * S, kLG, D);
+    }
     return true;
 }
 
@@ -403,10 +411,19 @@ extern "C" int cpc_lstm_layout(int B, int S, int nl, long* sizes) {
     return 0;
 }
 
-extern "C" int cpc_lstm_forward(const float* x, const float* h0, const float* c0, const float* const* params, float* saved,
-                                float* scratch, float* y, float* hN, float* cN, int B, int S, int nl, int flags, void* stream) {
+extern "C" int cpc_lstm_layout_in(int B, int S, int nl, int D, long* sizes) {
     LstmLayout g;
-    CPC_RETURN_IF(!lstm_layout(B, S, nl, g), CPC_ERR_SHAPE);
+    CPC_RETURN_IF(!lstm_layout(B, S, nl, g, D), CPC_ERR_SHAPE);
+    CPC_RETURN_IF(!sizes, CPC_ERR_ARG);
+    sizes[0] = g.saved_total; sizes[1] = g.fwd_total; sizes[2] = g.bwd_total;
+    return 0;
+}
+
+// D: x is (B,S,D) and weight_ih_l0 (4H,D); D == 256 is cpc_lstm_forward itself
+static int lstm_forward_impl(const float* x, const float* h0, const float* c0, const float* const* params, float* saved,
+                             float* scratch, float* y, float* hN, float* cN, int B, int S, int nl, int D, int flags, void* stream) {
+    LstmLayout g;
+    CPC_RETURN_IF(!lstm_layout(B, S, nl, g, D), CPC_ERR_SHAPE);
     CPC_RETURN_IF(flags & ~CPC_LSTM_PER_STEP, CPC_ERR_ARG);
     CPC_RETURN_IF(!x || !lstm_ptrs_ok(params, 4 * nl) || !saved || !scratch || !y || !hN || !cN, CPC_ERR_ARG);
     CPC_RETURN_IF((h0 == nullptr) != (c0 == nullptr), CPC_ERR_ARG);
@@ -419,7 +436,8 @@ extern "C" int cpc_lstm_forward(const float* x, const float* h0, const float* c0
     for (int l = 0; l < nl; ++l) {
         const float* wih = params[4 * l], *bih = params[4 * l + 2];
         float* out = l == nl - 1 ? y : saved + g.Y[l];
-        int rc = nt_gemm(plain_rows(in, M, kLH), wih, kLH, bih, gx, kLG, kLG, kLH, st);
+        int rc = l == 0 && D != kLH ? in_proj_forward(x, D, wih, bih, scratch + g.ipf, gx, M, kLG, D, st)
+                                    : nt_gemm(plain_rows(in, M, kLH), wih, kLH, bih, gx, kLG, kLG, kLH, st);
         if (rc) return rc;
         LstmFwd p;
         p.gx = gx; p.whh = params[4 * l + 1]; p.bhh = params[4 * l + 3];
@@ -440,11 +458,22 @@ extern "C" int cpc_lstm_forward(const float* x, const float* h0, const float* c0
     return 0;
 }
 
-extern "C" int cpc_lstm_backward(const float* x, const float* h0, const float* c0, const float* const* params, const float* saved,
-                                 const float* y, const float* dy, float* scratch, float* dx, float* const* grads, int B, int S,
-                                 int nl, int flags, void* stream) {
+extern "C" int cpc_lstm_forward(const float* x, const float* h0, const float* c0, const float* const* params, float* saved,
+                                float* scratch, float* y, float* hN, float* cN, int B, int S, int nl, int flags, void* stream) {
+    return lstm_forward_impl(x, h0, c0, params, saved, scratch, y, hN, cN, B, S, nl, kLH, flags, stream);
+}
+
+extern "C" int cpc_lstm_forward_in(const float* x, const float* h0, const float* c0, const float* const* params, float* saved,
+                                   float* scratch, float* y, float* hN, float* cN, int B, int S, int nl, int D, int flags,
+                                   void* stream) {
+    return lstm_forward_impl(x, h0, c0, params, saved, scratch, y, hN, cN, B, S, nl, D, flags, stream);
+}
+
+static int lstm_backward_impl(const float* x, const float* h0, const float* c0, const float* const* params, const float* saved,
+                              const float* y, const float* dy, float* scratch, float* dx, float* const* grads, int B, int S,
+                              int nl, int D, int flags, void* stream) {
     LstmLayout g;
-    CPC_RETURN_IF(!lstm_layout(B, S, nl, g), CPC_ERR_SHAPE);
+    CPC_RETURN_IF(!lstm_layout(B, S, nl, g, D), CPC_ERR_SHAPE);
     CPC_RETURN_IF(flags & ~CPC_LSTM_PER_STEP, CPC_ERR_ARG);
     CPC_RETURN_IF(!x || !lstm_ptrs_ok(params, 4 * nl) || !saved || !y || !dy || !scratch || !dx ||
                   !lstm_ptrs_ok(const_cast<const float* const*>(grads), 4 * nl), CPC_ERR_ARG);
@@ -462,7 +491,8 @@ extern "C" int cpc_lstm_backward(const float* x, const float* h0, const float* c
         float* dXl = l == 0 ? dx : scratch + g.mid[l & 1];
         int rc = transpose(params[4 * l + 1], whhT, kLG, kLH, st);      // (4H,H) -> (H,4H)
         if (rc) return rc;
-        rc = transpose(params[4 * l], wihT, kLG, kLH, st);
+        const bool narrow = l == 0 && D != kLH;          // layer 0 at another input width: its three products in in_proj.hip
+        rc = narrow ? 0 : transpose(params[4 * l], wihT, kLG, kLH, st);
         if (rc) return rc;
         LstmBwd p;
         p.whhT = whhT; p.dY = dYl; p.G = saved + g.G[l]; p.C = saved + g.C[l];
@@ -477,7 +507,8 @@ extern "C" int cpc_lstm_backward(const float* x, const float* h0, const float* c
         CPC_LAUNCH_CHECK();
         // weight / bias gradients over all B*S rows: dW_ih = dG^T . in, dW_hh = dG^T . h_{t-1}, db_ih = db_hh = sum dG
         const RowMap gm = plain_rows(dG, M, kLG);
-        rc = tn_gemm(gm, kLG, plain_rows(in, M, kLH), kLH, scratch + g.part, grads[4 * l], 0, st);
+        rc = narrow ? in_proj_backward(x, D, params[0], dG, scratch + g.ipb, nullptr, grads[0], M, kLG, D, st)
+                    : tn_gemm(gm, kLG, plain_rows(in, M, kLH), kLH, scratch + g.part, grads[4 * l], 0, st);
         if (rc) return rc;
         RowMap hm;                                       // h_{t-1} rows: out[b, t-1] (zero row at t = 0; h0 term below)
         hm.base = out; hm.R = S; hm.bstride = (long)S * kLH; hm.rstride = kLH; hm.off = -kLH;
@@ -495,11 +526,24 @@ extern "C" int cpc_lstm_backward(const float* x, const float* h0, const float* c
         if (rc) return rc;
         rc = rows_sum(dG, M, kLG, scratch + g.tmp, grads[4 * l + 3], st);
         if (rc) return rc;
-        rc = nt_gemm(gm, wihT, kLG, nullptr, dXl, kLH, kLH, kLG, st);   // dX = dG . W_ih (as NT against W_ih^T)
+        rc = narrow ? in_proj_backward(x, D, params[0], dG, scratch + g.ipb, dx, nullptr, M, kLG, D, st)
+                    : nt_gemm(gm, wihT, kLG, nullptr, dXl, kLH, kLH, kLG, st);   // dX = dG . W_ih (as NT against W_ih^T)
         if (rc) return rc;
         dYl = dXl;
     }
     return 0;
+}
+
+extern "C" int cpc_lstm_backward(const float* x, const float* h0, const float* c0, const float* const* params, const float* saved,
+                                 const float* y, const float* dy, float* scratch, float* dx, float* const* grads, int B, int S,
+                                 int nl, int flags, void* stream) {
+    return lstm_backward_impl(x, h0, c0, params, saved, y, dy, scratch, dx, grads, B, S, nl, kLH, flags, stream);
+}
+
+extern "C" int cpc_lstm_backward_in(const float* x, const float* h0, const float* c0, const float* const* params,
+                                    const float* saved, const float* y, const float* dy, float* scratch, float* dx,
+                                    float* const* grads, int B, int S, int nl, int D, int flags, void* stream) {
+    return lstm_backward_impl(x, h0, c0, params, saved, y, dy, scratch, dx, grads, B, S, nl, D, flags, stream);
 }
 
 // ---- G heads side by side (the criterion's --rnnMode LSTM predictors): see include/cpc_hip.h

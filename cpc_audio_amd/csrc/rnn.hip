@@ -179,10 +179,13 @@ struct RnnLayout {
     long saved_total;
     long gx, fwd_total;
     long whhT, wihT, dP, mid[2], part, tmp, bwd_total;
+    long ipf, ipb;        // D != 256: in_proj.hip's scratch behind the forward's / the backward's (the totals include it)
 };
 
-static bool rnn_layout(int T, int R, int G, int nl, RnnLayout& g) {
+// D: the input width of layer 0 (cpc_rnn_*_in, one head); at 256 the layout is the one cpc_rnn_layout has always reported
+static bool rnn_layout(int T, int R, int G, int nl, RnnLayout& g, int D = kRH) {
     if (T <= 0 || R <= 0 || G <= 0 || G > 64 || nl <= 0 || nl > 8) return false;
+    if (D < 1 || D > kInProjMaxD || (D != kRH && G != 1)) return false;
     if (G > 1 && nl > 1) return false;                                    // stacked layers exist for one head only
     if ((long)T * R > (1L << 21) || (long)T * R * G > (1L << 21)) return false;     // int GEMM rows and offsets
     const long M = (long)T * R, mh = align64l(M * kRH), mg = align64l(M * G * kRH);
@@ -204,6 +207,11 @@ static bool rnn_layout(int T, int R, int G, int nl, RnnLayout& g) {
     g.part = o; o += align64l(pa > pb ? pa : pb);
     g.tmp = o; o += align64l((long)kRowsSumGroups * G * kRH);
     g.bwd_total = o;
+    g.ipf = g.fwd_total; g.ipb = g.bwd_total;
+    if (D != kRH) {
+        g.fwd_total += in_proj_w_floats(kRH, D);
+        g.bwd_total += in_proj_scratch_floats(M, kRH, D);
+    }
     return true;
 }
 
@@ -261,10 +269,19 @@ extern "C" int cpc_rnn_layout(int T, int R, int G, int nl, long* sizes) {
     return 0;
 }
 
-extern "C" int cpc_rnn_forward(const float* x, const float* h0, const float* const* params, float* saved, float* scratch, float* y,
-                               float* hN, int T, int R, int G, int nl, int flags, void* stream) {
+extern "C" int cpc_rnn_layout_in(int T, int R, int nl, int D, long* sizes) {
     RnnLayout g;
-    CPC_RETURN_IF(!rnn_layout(T, R, G, nl, g), CPC_ERR_SHAPE);
+    CPC_RETURN_IF(!rnn_layout(T, R, 1, nl, g, D), CPC_ERR_SHAPE);
+    CPC_RETURN_IF(!sizes, CPC_ERR_ARG);
+    sizes[0] = g.saved_total; sizes[1] = g.fwd_total; sizes[2] = g.bwd_total;
+    return 0;
+}
+
+// D: x is (.,.,D) and weight_ih_l0 (H,D), one head, either layout (the projection works row by row); D == 256 is cpc_rnn_forward itself
+static int rnn_forward_impl(const float* x, const float* h0, const float* const* params, float* saved, float* scratch, float* y,
+                            float* hN, int T, int R, int G, int nl, int D, int flags, void* stream) {
+    RnnLayout g;
+    CPC_RETURN_IF(!rnn_layout(T, R, G, nl, g, D), CPC_ERR_SHAPE);
     CPC_RETURN_IF(flags & ~(CPC_RNN_PER_STEP | CPC_RNN_TIME_MAJOR), CPC_ERR_ARG);
     CPC_RETURN_IF(!x || !rnn_ptrs_ok(params, 4 * nl) || !saved || !scratch || !y, CPC_ERR_ARG);
     CPC_RETURN_IF(G > 1 && (h0 || hN), CPC_ERR_ARG);                     // carried and final state exist for one head only
@@ -275,7 +292,9 @@ extern "C" int cpc_rnn_forward(const float* x, const float* h0, const float* con
     const float* in = x;
     for (int l = 0; l < nl; ++l) {
         float* out = l == nl - 1 ? y : saved + g.Y[l];
-        int rc = nt_gemm(plain_rows(in, M, kRH), params[4 * l], kRH, params[4 * l + 2], gx, (long)G * kRH, G * kRH, kRH, st);
+        int rc = l == 0 && D != kRH
+                     ? in_proj_forward(x, D, params[0], params[2], scratch + g.ipf, gx, M, kRH, D, st)
+                     : nt_gemm(plain_rows(in, M, kRH), params[4 * l], kRH, params[4 * l + 2], gx, (long)G * kRH, G * kRH, kRH, st);
         if (rc) return rc;
         RnnRec p;
         p.w = params[4 * l + 1]; p.add = gx; p.bias = params[4 * l + 3];
@@ -289,11 +308,21 @@ extern "C" int cpc_rnn_forward(const float* x, const float* h0, const float* con
     return 0;
 }
 
-extern "C" int cpc_rnn_backward(const float* x, const float* h0, const float* const* params, const float* saved, const float* y,
-                                const float* dy, float* scratch, float* dx, float* const* grads, int T, int R, int G, int nl,
-                                int flags, void* stream) {
+extern "C" int cpc_rnn_forward(const float* x, const float* h0, const float* const* params, float* saved, float* scratch, float* y,
+                               float* hN, int T, int R, int G, int nl, int flags, void* stream) {
+    return rnn_forward_impl(x, h0, params, saved, scratch, y, hN, T, R, G, nl, kRH, flags, stream);
+}
+
+extern "C" int cpc_rnn_forward_in(const float* x, const float* h0, const float* const* params, float* saved, float* scratch,
+                                  float* y, float* hN, int T, int R, int nl, int D, int flags, void* stream) {
+    return rnn_forward_impl(x, h0, params, saved, scratch, y, hN, T, R, 1, nl, D, flags, stream);
+}
+
+static int rnn_backward_impl(const float* x, const float* h0, const float* const* params, const float* saved, const float* y,
+                             const float* dy, float* scratch, float* dx, float* const* grads, int T, int R, int G, int nl, int D,
+                             int flags, void* stream) {
     RnnLayout g;
-    CPC_RETURN_IF(!rnn_layout(T, R, G, nl, g), CPC_ERR_SHAPE);
+    CPC_RETURN_IF(!rnn_layout(T, R, G, nl, g, D), CPC_ERR_SHAPE);
     CPC_RETURN_IF(flags & ~(CPC_RNN_PER_STEP | CPC_RNN_TIME_MAJOR), CPC_ERR_ARG);
     CPC_RETURN_IF(!x || !rnn_ptrs_ok(params, 4 * nl) || !saved || !y || !dy || !scratch || !dx ||
                   !rnn_ptrs_ok(const_cast<const float* const*>(grads), 4 * nl), CPC_ERR_ARG);
@@ -312,7 +341,8 @@ extern "C" int cpc_rnn_backward(const float* x, const float* h0, const float* co
         float* dXl = l == 0 ? dx : scratch + g.mid[l & 1];
         int rc = transpose(params[4 * l + 1], whhT, kRH, kRH, st, G, (long)kRH * kRH, (long)kRH * kRH);   // per head
         if (rc) return rc;
-        rc = transpose(params[4 * l], wihT, G * kRH, kRH, st);                // stacked (G H,H) -> (H,G H)
+        const bool narrow = l == 0 && D != kRH;          // layer 0 at another input width: its three products in in_proj.hip
+        rc = narrow ? 0 : transpose(params[4 * l], wihT, G * kRH, kRH, st);   // stacked (G H,H) -> (H,G H)
         if (rc) return rc;
         RnnRec p;
         p.w = whhT; p.add = dYl; p.bias = nullptr; p.first = nullptr; p.yv = out; p.out = dP; p.last = nullptr;
@@ -321,7 +351,8 @@ extern "C" int cpc_rnn_backward(const float* x, const float* h0, const float* co
         if (rc) return rc;
         // over all T*R rows: stacked dW_ih = dP^T . in, dW_hh = dP^T . h_{t-1} head by head in one launch, db_ih = db_hh = sum dP
         const RowMap gm = plain_rows(dP, M, G * kRH);
-        rc = tn_gemm(gm, G * kRH, plain_rows(in, M, kRH), kRH, scratch + g.part, grads[4 * l], 0, st);
+        rc = narrow ? in_proj_backward(x, D, params[0], dP, scratch + g.ipb, nullptr, grads[0], M, kRH, D, st)
+                    : tn_gemm(gm, G * kRH, plain_rows(in, M, kRH), kRH, scratch + g.part, grads[4 * l], 0, st);
         if (rc) return rc;
         RowMap hm;                                       // h_{t-1} rows of head 0 (zero rows at t = 0; h0 term below)
         hm.base = out; hm.rstride = (int)hs; hm.tmul = 1; hm.M = M;
@@ -342,9 +373,22 @@ extern "C" int cpc_rnn_backward(const float* x, const float* h0, const float* co
         if (rc) return rc;
         rc = rows_sum(dP, M, G * kRH, scratch + g.tmp, grads[4 * l + 3], st);
         if (rc) return rc;
-        rc = nt_gemm(gm, wihT, G * kRH, nullptr, dXl, kRH, kRH, G * kRH, st);     // dX = dP . W_ih, summed over the heads
+        rc = narrow ? in_proj_backward(x, D, params[0], dP, scratch + g.ipb, dx, nullptr, M, kRH, D, st)
+                    : nt_gemm(gm, wihT, G * kRH, nullptr, dXl, kRH, kRH, G * kRH, st);     // dX = dP . W_ih, summed over the heads
         if (rc) return rc;
         dYl = dXl;
     }
     return 0;
+}
+
+extern "C" int cpc_rnn_backward(const float* x, const float* h0, const float* const* params, const float* saved, const float* y,
+                                const float* dy, float* scratch, float* dx, float* const* grads, int T, int R, int G, int nl,
+                                int flags, void* stream) {
+    return rnn_backward_impl(x, h0, params, saved, y, dy, scratch, dx, grads, T, R, G, nl, kRH, flags, stream);
+}
+
+extern "C" int cpc_rnn_backward_in(const float* x, const float* h0, const float* const* params, const float* saved, const float* y,
+                                   const float* dy, float* scratch, float* dx, float* const* grads, int T, int R, int nl, int D,
+                                   int flags, void* stream) {
+    return rnn_backward_impl(x, h0, params, saved, y, dy, scratch, dx, grads, T, R, 1, nl, D, flags, stream);
 }

@@ -258,12 +258,21 @@ class CPCAR(nn.Module):
     (HIP, ``self.hip_lstm``) for CUDA fp32 input; baseNet stays the nn.LSTM parameter container.  ``rnnKernel=True`` does the same
     for mode ``RNN``: nn.RNN(256, 256, nLevelsGRU, batch_first=True) of 1..8 layers through cpc_rnn_forward (HIP,
     ``self.hip_rnn``), baseNet the nn.RNN parameter container.  ``self.hip`` keeps meaning the GRU kernel (what the fused train
-    step checks)."""
+    step checks).
+    ``inputKernel=True`` (default off, as the two above) takes an encoder width other than 256 -- 1 <= dimEncoded <= 512,
+    dimOutput == 256, 1..8 layers: MFCC at 13 / 40 / 80 coefficients, the learned filter bank at 64, CPCEncoder(512) -- to the
+    same HIP recurrences for CUDA fp32 input (``self.hip_in``): layer 0's input projection runs at its true width
+    (csrc/in_proj.hip, cpc_*_forward_in).  Mode GRU needs nothing else; LSTM and RNN also need their own keyword.  ``self.hip``,
+    ``self.hip_lstm`` and ``self.hip_rnn`` stay False at such a width: they keep meaning the 256 -> 256 kernels."""
 
     def __init__(self, dimEncoded, dimOutput, keepHidden, nLevelsGRU, mode="GRU", reverse=False, lstmKernel=False,
-                 rnnKernel=False):
+                 rnnKernel=False, inputKernel=False):
         super().__init__()
         self.RESIDUAL_STD = 0.1
+        self._cell = mode if mode in ("LSTM", "RNN") else "GRU"
+        self.hip_in = (bool(inputKernel) and dimOutput == 256 and dimEncoded != 256 and 1 <= dimEncoded <= ops.IN_PROJ_MAX
+                       and 1 <= nLevelsGRU <= 8
+                       and (self._cell == "GRU" or bool(lstmKernel if self._cell == "LSTM" else rnnKernel)))
         self.hip = mode not in ("LSTM", "RNN") and dimEncoded == 256 and dimOutput == 256
         self.hip_lstm = bool(lstmKernel) and mode == "LSTM" and dimEncoded == 256 and dimOutput == 256
         self.hip_rnn = (bool(rnnKernel) and mode == "RNN" and dimEncoded == 256 and dimOutput == 256
@@ -287,7 +296,8 @@ class CPCAR(nn.Module):
         """(B, S, 256) -> (B, S, 256).  In reverse mode the sequence is processed back to front and handed back in its
         original order (cpc/model.py:185-204); the final hidden state is kept for the next call when keepHidden is set."""
         flip = (lambda t: torch.flip(t, [1])) if self.reverse else (lambda t: t)
-        if self.hip_lstm and x.is_cuda and x.dtype == torch.float32:
+        narrow = self.hip_in and x.is_cuda and x.dtype == torch.float32      # (another input width: the same Functions, cpc_*_in)
+        if (self.hip_lstm or narrow and self._cell == "LSTM") and x.is_cuda and x.dtype == torch.float32:
             y, hN, cN = LstmFunction.apply(flip(x), self.hidden, False, *self._flat_params())
             if self.keepHidden:
                 self.hidden = (hN.detach(), cN.detach())
@@ -296,14 +306,14 @@ class CPCAR(nn.Module):
             # the output never carries the initial state through, so no check of where self.hidden came from is needed
             out._cpc_abs_bound = 1.0
             return out
-        if self.hip_rnn and x.is_cuda and x.dtype == torch.float32:
+        if (self.hip_rnn or narrow and self._cell == "RNN") and x.is_cuda and x.dtype == torch.float32:
             y, hN = RnnFunction.apply(flip(x), self.hidden, False, False, *self._flat_params())
             if self.keepHidden:
                 self.hidden = hN.detach()
             out = flip(y)
             out._cpc_abs_bound = 1.0                           # |tanh| <= 1 whatever h0 is
             return out
-        if not self.hip:                                       # cpc/model.py:185-204 with baseNet's own torch forward
+        if not (self.hip or narrow):                           # cpc/model.py:185-204 with baseNet's own torch forward
             y, h = self.baseNet(flip(x), self.hidden)
             if self.keepHidden:
                 self.hidden = tuple(t.detach() for t in h) if isinstance(h, tuple) else h.detach()

@@ -415,8 +415,23 @@ class EncoderFunction(torch.autograd.Function):
         return (None, *grads)
 
 
+IN_PROJ_MAX = 512      # widest layer-0 input of the recurrent cells (cpc_*_in; csrc/in_proj.hip)
+
+
+def _cell_input_width(x, params, gates, what):
+    """The input width D of a cell whose weight_ih_l0 is (gates * 256, D) and weight_hh_l0 (gates * 256, 256)."""
+    D = x.shape[2]
+    if (not 1 <= D <= IN_PROJ_MAX or tuple(params[0].shape) != (gates * _HID, D)
+            or params[1].numel() != gates * _HID * _HID):
+        raise NotImplementedError(f"the HIP {what} is built for dimOutput == 256 and 1 <= dimEncoded <= {IN_PROJ_MAX} "
+                                  f"(x {tuple(x.shape)}, weight_ih_l0 {tuple(params[0].shape)})")
+    return D
+
+
 class GruFunction(torch.autograd.Function):
-    """x (B,S,256), h0 (nl,B,256) or None, 4*nl GRU parameters -> y (B,S,256), hN (nl,B,256)."""
+    """x (B,S,D), h0 (nl,B,256) or None, 4*nl GRU parameters -> y (B,S,256), hN (nl,B,256).  D == 256 is the path of the fused
+    step (prepared coefficients, weight gradients on their own stream); any other D in 1..512 -- weight_ih_l0 (768, D) -- runs
+    cpc_gru_forward_in / _backward_in: layer 0's input projection in csrc/in_proj.hip, the same recurrences, one stream."""
 
     @staticmethod
     def forward(ctx, x, h0, *params):
@@ -425,11 +440,28 @@ class GruFunction(torch.autograd.Function):
         B, S, D = x.shape
         nl = len(params) // 4
         leaves = params                           # the tensors autograd knows (normally the module's Parameters)
-        if D != _HID or params[1].shape != (3 * _HID, _HID):
-            raise NotImplementedError("the HIP GRU is built for dimEncoded == dimOutput == 256")
+        D = _cell_input_width(x, params, 3, "GRU")
         x = x.contiguous()
         params = [p.detach().contiguous() for p in params]
         h0c = None if h0 is None else h0.detach().contiguous()
+        if D != _HID:
+            with torch.cuda.device(x.device):
+                sizes = _layout("gru_layout_in", lib.cpc_gru_layout_in, 3, B, S, nl, D)
+                saved = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
+                scratch = torch.empty(sizes[1], device=x.device, dtype=torch.float32)
+                y = torch.empty(B, S, _HID, device=x.device, dtype=torch.float32)
+                hN = torch.empty(nl, B, _HID, device=x.device, dtype=torch.float32)
+                lib.check(lib.cpc_gru_forward_in(_p(x), _p(h0c), _ptrs(params), _p(saved), _p(scratch), _p(y), _p(hN), B, S, nl, D,
+                                                 _stream()), "gru_forward_in")
+            ctx.step = current()
+            ctx.coef = None
+            ctx.leaves = None
+            ctx.save_for_backward(x, saved, y, *params)
+            ctx.h0 = h0c
+            ctx.dims = (B, S, nl, sizes[2])
+            ctx.mark_non_differentiable(hN)
+            ctx.set_materialize_grads(False)
+            return y, hN
         with torch.cuda.device(x.device):
             sizes = _layout("gru_layout", lib.cpc_gru_layout, 3, B, S, nl)
             saved = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
@@ -483,8 +515,12 @@ class GruFunction(torch.autograd.Function):
             if ctx.coef is not None:
                 torch.cuda.current_stream().wait_event(ctx.coef_ready)
             step = ctx.step
+            D = x.shape[2]
             split = _overlap(step) and step.wgrad_stream and nl == 2 and ctx.leaves is not None
-            if split:
+            if D != _HID:
+                lib.check(lib.cpc_gru_backward_in(_p(x), _p(ctx.h0), _ptrs(params), _p(saved), _p(y), _p(dy), _p(scratch), _p(dx),
+                                                  _ptrs(grads), B, S, nl, D, _stream()), "gru_backward_in")
+            elif split:
                 # dx on this stream; the weight / bias gradients -- read by nobody before the optimiser -- on the
                 # weight-gradient stream, beside the start of the encoder's backward.  They are added to .grad there
                 # (autograd gets None for them: it would accumulate on this stream, before they exist).
@@ -522,7 +558,8 @@ class LstmFunction(torch.autograd.Function):
 
     The carried state is an input only: neither h0 nor c0 receives a gradient (the reference detaches it between calls,
     cpc/model.py:194-198), and hN / cN are not differentiable.  per_step: the one-launch-per-step kernels instead of the
-    persistent recurrence (same bits; tests)."""
+    persistent recurrence (same bits; tests).  x may be (B,S,D) with weight_ih_l0 (1024, D), 1 <= D <= 512: layer 0's input
+    projection then runs in csrc/in_proj.hip (cpc_lstm_forward_in / _backward_in)."""
 
     @staticmethod
     def forward(ctx, x, state, per_step, *params):
@@ -530,21 +567,25 @@ class LstmFunction(torch.autograd.Function):
         lib = _lib.get()
         B, S, D = x.shape
         nl = len(params) // 4
-        if D != _HID or params[1].shape != (4 * _HID, _HID):
-            raise NotImplementedError("the HIP LSTM is built for dimEncoded == dimOutput == 256")
+        D = _cell_input_width(x, params, 4, "LSTM")              # (D != 256: weight_ih_l0 (1024, D), cpc_lstm_*_in)
         x = x.contiguous()
         params = [p.detach().contiguous() for p in params]
         h0, c0 = (None, None) if state is None else (state[0].detach().contiguous(), state[1].detach().contiguous())
         flags = 1 if per_step else 0                      # CPC_LSTM_PER_STEP
         with torch.cuda.device(x.device):
-            sizes = _layout("lstm_layout", lib.cpc_lstm_layout, 3, B, S, nl)
+            sizes = _layout("lstm_layout_in", lib.cpc_lstm_layout_in, 3, B, S, nl, D) if D != _HID else \
+                _layout("lstm_layout", lib.cpc_lstm_layout, 3, B, S, nl)
             saved = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
             scratch = torch.empty(sizes[1], device=x.device, dtype=torch.float32)
             y = torch.empty(B, S, _HID, device=x.device, dtype=torch.float32)
             hN = torch.empty(nl, B, _HID, device=x.device, dtype=torch.float32)
             cN = torch.empty(nl, B, _HID, device=x.device, dtype=torch.float32)
-            lib.check(lib.cpc_lstm_forward(_p(x), _p(h0), _p(c0), _ptrs(params), _p(saved), _p(scratch), _p(y), _p(hN), _p(cN),
-                                           B, S, nl, flags, _stream()), "lstm_forward")
+            if D != _HID:
+                lib.check(lib.cpc_lstm_forward_in(_p(x), _p(h0), _p(c0), _ptrs(params), _p(saved), _p(scratch), _p(y), _p(hN),
+                                                  _p(cN), B, S, nl, D, flags, _stream()), "lstm_forward_in")
+            else:
+                lib.check(lib.cpc_lstm_forward(_p(x), _p(h0), _p(c0), _ptrs(params), _p(saved), _p(scratch), _p(y), _p(hN), _p(cN),
+                                               B, S, nl, flags, _stream()), "lstm_forward")
         ctx.save_for_backward(x, saved, y, *params)
         ctx.state = (h0, c0)
         ctx.dims = (B, S, nl, sizes[2], flags)
@@ -563,8 +604,12 @@ class LstmFunction(torch.autograd.Function):
             scratch = torch.empty(nscr, device=x.device, dtype=torch.float32)
             dx = torch.empty_like(x)
             grads = [torch.empty_like(p) for p in params]
-            lib.check(lib.cpc_lstm_backward(_p(x), _p(h0), _p(c0), _ptrs(params), _p(saved), _p(y), _p(dy), _p(scratch), _p(dx),
-                                            _ptrs(grads), B, S, nl, flags, _stream()), "lstm_backward")
+            if x.shape[2] != _HID:
+                lib.check(lib.cpc_lstm_backward_in(_p(x), _p(h0), _p(c0), _ptrs(params), _p(saved), _p(y), _p(dy), _p(scratch),
+                                                   _p(dx), _ptrs(grads), B, S, nl, x.shape[2], flags, _stream()), "lstm_backward_in")
+            else:
+                lib.check(lib.cpc_lstm_backward(_p(x), _p(h0), _p(c0), _ptrs(params), _p(saved), _p(y), _p(dy), _p(scratch), _p(dx),
+                                                _ptrs(grads), B, S, nl, flags, _stream()), "lstm_backward")
         return (dx, None, None, *grads)
 
 
@@ -638,16 +683,25 @@ class RnnFunction(torch.autograd.Function):
     -> y (R,T,G*256) -- the batch_first autoregressor (G = 1).  params: per layer weight_ih (G*256,256), weight_hh (G,256,256) or
     (256,256), bias_ih, bias_hh (G*256): the heads' tensors one behind the other; G > 1 only with one layer and without h0.
     h0: None or (nl,R,256); it receives no gradient (the reference detaches the carried state, cpc/model.py:194-198).
-    -> y, hN (nl,R,256; not differentiable; None for G > 1).  per_step: one launch per step (same bits; tests)."""
+    -> y, hN (nl,R,256; not differentiable; None for G > 1).  per_step: one launch per step (same bits; tests).
+    One head (G = 1) also takes x of width D with weight_ih_l0 (256, D), 1 <= D <= 512, in either layout (cpc_rnn_forward_in /
+    _backward_in)."""
 
     @staticmethod
     def forward(ctx, x, h0, time_major, per_step, *params):
         _require_cuda(x, "RnnFunction")
         lib = _lib.get()
         nl = len(params) // 4
-        if (x.dim() != 3 or x.shape[2] != _HID or nl < 1 or len(params) != 4 * nl or params[0].shape[0] % _HID
-                or any(tuple(params[4 * l].shape) != tuple(params[0].shape) or params[4 * l].shape[1] != _HID
-                       or params[4 * l + 1].numel() != params[0].numel() or params[4 * l + 2].numel() != params[0].shape[0]
+        # another input width D in 1..512 (weight_ih_l0 (256, D)): one head -- cpc_rnn_*_in
+        D = x.shape[2] if x.dim() == 3 else _HID
+        narrow = D != _HID
+        if narrow and (nl < 1 or len(params) != 4 * nl or not 1 <= D <= IN_PROJ_MAX
+                       or tuple(params[0].shape) != (_HID, D)):
+            raise NotImplementedError("cpc_audio_amd.RnnFunction: an input width other than 256 takes one head with "
+                                      f"weight_ih_l0 (256, D), 1 <= D <= {IN_PROJ_MAX}")
+        if (x.dim() != 3 or nl < 1 or len(params) != 4 * nl or params[0].shape[0] % _HID
+                or any(params[4 * l].shape[0] != params[0].shape[0] or (params[4 * l].shape[1] != _HID and (l > 0 or not narrow))
+                       or params[4 * l + 1].numel() != params[0].shape[0] * _HID or params[4 * l + 2].numel() != params[0].shape[0]
                        or params[4 * l + 3].numel() != params[0].shape[0] for l in range(nl))):
             raise NotImplementedError("cpc_audio_amd.RnnFunction: x (.,.,256) and stacked nn.RNN(256, 256) parameters expected")
         G = params[0].shape[0] // _HID
@@ -657,13 +711,18 @@ class RnnFunction(torch.autograd.Function):
         h0 = None if h0 is None else h0.detach().contiguous()
         flags = (1 if per_step else 0) | (2 if time_major else 0)       # CPC_RNN_PER_STEP, CPC_RNN_TIME_MAJOR
         with torch.cuda.device(x.device):
-            sizes = _layout("rnn_layout", lib.cpc_rnn_layout, 3, T, R, G, nl)
+            sizes = _layout("rnn_layout_in", lib.cpc_rnn_layout_in, 3, T, R, nl, D) if narrow else \
+                _layout("rnn_layout", lib.cpc_rnn_layout, 3, T, R, G, nl)
             saved = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
             scratch = torch.empty(sizes[1], device=x.device, dtype=torch.float32)
             y = torch.empty(x.shape[0], x.shape[1], G * _HID, device=x.device, dtype=torch.float32)
             hN = torch.empty(nl, R, _HID, device=x.device, dtype=torch.float32) if G == 1 else None
-            lib.check(lib.cpc_rnn_forward(_p(x), _p(h0), _ptrs(params), _p(saved), _p(scratch), _p(y), _p(hN), T, R, G, nl, flags,
-                                          _stream()), "rnn_forward")
+            if narrow:
+                lib.check(lib.cpc_rnn_forward_in(_p(x), _p(h0), _ptrs(params), _p(saved), _p(scratch), _p(y), _p(hN), T, R, nl, D,
+                                                 flags, _stream()), "rnn_forward_in")
+            else:
+                lib.check(lib.cpc_rnn_forward(_p(x), _p(h0), _ptrs(params), _p(saved), _p(scratch), _p(y), _p(hN), T, R, G, nl, flags,
+                                              _stream()), "rnn_forward")
         ctx.save_for_backward(x, saved, y, *params)
         ctx.h0 = h0
         ctx.dims = (T, R, G, nl, sizes[2], flags)
@@ -682,8 +741,12 @@ class RnnFunction(torch.autograd.Function):
             scratch = torch.empty(nscr, device=x.device, dtype=torch.float32)
             dx = torch.empty_like(x)
             grads = [torch.empty_like(p) for p in params]
-            lib.check(lib.cpc_rnn_backward(_p(x), _p(ctx.h0), _ptrs(params), _p(saved), _p(y), _p(dy), _p(scratch), _p(dx),
-                                           _ptrs(grads), T, R, G, nl, flags, _stream()), "rnn_backward")
+            if x.shape[2] != _HID:
+                lib.check(lib.cpc_rnn_backward_in(_p(x), _p(ctx.h0), _ptrs(params), _p(saved), _p(y), _p(dy), _p(scratch), _p(dx),
+                                                  _ptrs(grads), T, R, nl, x.shape[2], flags, _stream()), "rnn_backward_in")
+            else:
+                lib.check(lib.cpc_rnn_backward(_p(x), _p(ctx.h0), _ptrs(params), _p(saved), _p(y), _p(dy), _p(scratch), _p(dx),
+                                               _ptrs(grads), T, R, G, nl, flags, _stream()), "rnn_backward")
         return (dx, None, None, None, *grads)
 
 

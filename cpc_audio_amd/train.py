@@ -13,14 +13,15 @@ from .optim import Adam
 
 def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False, reverse=False, arMode="GRU",
                 sizeWindow=20480, abspos=False, transformerDropout=0.1, lstmKernel=False, encoder_type="cpc", rnnKernel=False,
-                mfccKernel=False):
+                mfccKernel=False, inputKernel=False):
     """cpc/feature_loader.py:124-153 (getEncoder / getAR) + cpc/train.py:311.  arMode 'GRU' (north star) or
     'transformer' (BASELINE.json config 4: buildTransformerAR(hiddenEncoder, 1, sizeWindow // 160, abspos)); 'LSTM' /
     'RNN' as the reference (lstmKernel / rnnKernel: the LSTM / the RNN on the HIP kernels, CPCAR); 'no_ar': the identity, and the context width is
     the encoder's (cpc/train.py:486).  encoder_type 'cpc' or 'lfb' (learned filter banks, LFBEnconder); 'mfcc' with
     mfccKernel=True (not in the reference's signature; default off, as lstmKernel / rnnKernel) builds MFCCEncoder, this package's
     restatement of torchaudio's MFCC on HIP kernels (hiddenEncoder coefficients); without the keyword 'mfcc' raises, since the
-    reference's class is torchaudio.transforms.MFCC and torchaudio is not a dependency."""
+    reference's class is torchaudio.transforms.MFCC and torchaudio is not a dependency.  inputKernel=True (default off likewise):
+    a GRU / LSTM / RNN autoregressor behind an encoder of another width than 256 runs the HIP recurrences too (CPCAR)."""
     if encoder_type == "mfcc" and not mfccKernel:
         raise NotImplementedError("encoder_type 'mfcc' is torchaudio.transforms.MFCC in the reference; torchaudio is not a "
                                   "dependency of this package.  Pass mfccKernel=True for MFCCEncoder, the package's own "
@@ -38,7 +39,7 @@ def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False
         ar = buildTransformerAR(hiddenEncoder, 1, sizeWindow // 160, abspos, dropout=transformerDropout)
     else:
         ar = CPCAR(hiddenEncoder, hiddenGar, keepHidden, nLevelsGRU, mode=arMode, reverse=reverse, lstmKernel=lstmKernel,
-                   rnnKernel=rnnKernel)
+                   rnnKernel=rnnKernel, inputKernel=inputKernel)
     return CPCModel(enc, ar)
 
 

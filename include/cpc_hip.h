@@ -368,6 +368,49 @@ int cpc_rnn_backward(const float* x, const float* h0, const float* const* params
                      const float* dy, float* scratch, float* dx, float* const* grads, int T, int R, int G, int nl, int flags,
                      void* stream);
 
+/* ------------------------------------------------------------ autoregressors at any input width ----
+ * The three cells above with an encoder width D in 1..512 in front of the 256-wide context (MFCC at 13 / 40 / 80 coefficients,
+ * the learned filter bank at 64, CPCEncoder(512) ...): x, dx are (B,S,D) -- for the RNN (R,T,D), or (T,R,D) with CPC_RNN_TIME_MAJOR, one head --
+ * and weight_ih_l0 and its gradient (3H | 4H | H, D); everything else is as in cpc_gru_* / cpc_lstm_* / cpc_rnn_* (same
+ * params / grads order, saved buffers, flags, carried state, error words).  Only layer 0's input projection and its two backward
+ * products depend on D; they run in csrc/in_proj.hip, the recurrences and the layers above are the 256-wide ones.  With D == 256
+ * the *_in entries ARE the plain entries: same launches, same bits, same layout sizes.  The GRU takes no prepared coefficients
+ * and no second stream here (cpc_gru_forward_coef / cpc_gru_backward_streams stay 256-wide).
+ * cpc_*_layout_in fill sizes[0..2] = saved / forward-scratch / backward-scratch floats.  D outside 1..512: CPC_ERR_SHAPE; a NULL
+ * pointer: CPC_ERR_ARG; both before any launch. */
+int cpc_gru_layout_in(int B, int S, int nl, int D, long* sizes);
+int cpc_gru_forward_in(const float* x, const float* h0, const float* const* params, float* saved, float* scratch, float* y,
+                       float* hN, int B, int S, int nl, int D, void* stream);
+int cpc_gru_backward_in(const float* x, const float* h0, const float* const* params, const float* saved, const float* y,
+                        const float* dy, float* scratch, float* dx, float* const* grads, int B, int S, int nl, int D, void* stream);
+int cpc_lstm_layout_in(int B, int S, int nl, int D, long* sizes);
+int cpc_lstm_forward_in(const float* x, const float* h0, const float* c0, const float* const* params, float* saved, float* scratch,
+                        float* y, float* hN, float* cN, int B, int S, int nl, int D, int flags, void* stream);
+int cpc_lstm_backward_in(const float* x, const float* h0, const float* c0, const float* const* params, const float* saved,
+                         const float* y, const float* dy, float* scratch, float* dx, float* const* grads, int B, int S, int nl,
+                         int D, int flags, void* stream);
+int cpc_rnn_layout_in(int T, int R, int nl, int D, long* sizes);
+int cpc_rnn_forward_in(const float* x, const float* h0, const float* const* params, float* saved, float* scratch, float* y,
+                       float* hN, int T, int R, int nl, int D, int flags, void* stream);
+int cpc_rnn_backward_in(const float* x, const float* h0, const float* const* params, const float* saved, const float* y,
+                        const float* dy, float* scratch, float* dx, float* const* grads, int T, int R, int nl, int D, int flags,
+                        void* stream);
+
+/* The projection on its own (csrc/in_proj.hip; exact-f32 MFMAs, so nothing is assumed about the size of x):
+ *   cpc_in_proj_forward   out[M,N] = x[M,D] . w[N,D]^T + bias            (bias may be NULL)
+ *   cpc_in_proj_backward  dx[M,D] = dg[M,N] . w[N,D]   and   dw[N,D] = dg[M,N]^T . x[M,D]   (both OVERWRITTEN; dx or dw may be
+ *                         NULL -- that product is skipped -- but not both)
+ * 1 <= M <= 2^24, N a multiple of 128 (<= 65536), 1 <= D <= 512 (CPC_ERR_SHAPE otherwise).  Row m of x and of dx starts at
+ * + m * ldx floats, ldx >= D, at any 4-byte alignment: nothing is read or written outside the D columns of the M rows.  w is
+ * contiguous; out, dg (N floats per row) and scratch must be 16-byte aligned (CPC_ERR_ARG otherwise, as for a NULL pointer).
+ * scratch: cpc_in_proj_scratch_floats(M, N, D) floats (0 for a shape outside the limits) -- a zero-padded copy of w and the row
+ * splits of dw, which are summed in a fixed order: no atomics, the same bits every run. */
+long cpc_in_proj_scratch_floats(int M, int N, int D);
+int cpc_in_proj_forward(const float* x, long ldx, const float* w, const float* bias, float* scratch, float* out, int M, int N,
+                        int D, void* stream);
+int cpc_in_proj_backward(const float* x, long ldx, const float* w, const float* dg, float* scratch, float* dx, float* dw, int M,
+                         int N, int D, void* stream);
+
 /* ------------------------------------------------------------ supervised criteria ----
  * SpeakerCriterion / PhoneCriterion (cpc/criterion/criterion.py:182-246): nn.Linear(256, C) + nn.CrossEntropyLoss() (mean)
  * and (argmax == label).double().mean(); CTCPhoneCriterion (criterion.py:249-283): the same linear layer, log_softmax and
