@@ -23,11 +23,13 @@
 //     the per-step kernels remain for other depths and as the path when the grid cannot be co-resident;
 //   * backward (BPTT) mirrors it with K = 768:  dh_t = dY_t + dh_{t+1} * z_{t+1}
 //     + dGh_{t+1} . W_hh,  then the gate derivatives; all weight gradients are batched
-//     TN GEMMs over the B*S rows afterwards.
+//     TN GEMMs over the B*S rows afterwards (the per-layer path: recurrent_host.h's GradTail, shared with lstm.hip and
+//     rnn.hip; the two-layer path keeps its own batched tail).
 #include "cpc_common.h"
 #include "cpc_internal.h"
 #include "gemm_tile.h"
 #include "persist.h"
+#include "recurrent_host.h"
 
 namespace cpc {
 
@@ -1295,12 +1297,7 @@ extern "C" int cpc_set_gru_mode(int mode) {
 }
 
 // sizes[0] = saved floats, [1] = forward scratch floats, [2] = backward scratch floats
-extern "C" int cpc_gru_layout(int B, int S, int nl, long* sizes) {
-    GruLayout g;
-    CPC_RETURN_IF(!gru_layout(B, S, nl, g), CPC_ERR_SHAPE);
-    sizes[0] = g.saved_total; sizes[1] = g.fwd_total; sizes[2] = g.bwd_total;
-    return 0;
-}
+extern "C" int cpc_gru_layout(int B, int S, int nl, long* sizes) { return cpc_gru_layout_in(B, S, nl, kH, sizes); }
 
 // x (B,S,256); h0 NULL or (nl,B,256); params: weight_ih, weight_hh, bias_ih, bias_hh per layer
 // (torch.nn.GRU state-dict order); y (B,S,256) = last layer's output; hN (nl,B,256) final states.
@@ -1338,10 +1335,7 @@ extern "C" int cpc_gru_forward_coef_prepared(const float* x, const float* h0, co
 // D: x is (B,S,D) and weight_ih_l0 (3H,D) (cpc_gru_forward_in); layer 0's input projection then runs in in_proj.hip
 extern "C" int cpc_gru_layout_in(int B, int S, int nl, int D, long* sizes) {
     GruLayout g;
-    CPC_RETURN_IF(!gru_layout(B, S, nl, g, D), CPC_ERR_SHAPE);
-    CPC_RETURN_IF(!sizes, CPC_ERR_ARG);
-    sizes[0] = g.saved_total; sizes[1] = g.fwd_total; sizes[2] = g.bwd_total;
-    return 0;
+    return layout_sizes(gru_layout(B, S, nl, g, D), g, sizes);
 }
 extern "C" int cpc_gru_forward_in(const float* x, const float* h0, const float* const* params, float* saved, float* scratch,
                                   float* y, float* hN, int B, int S, int nl, int D, void* stream) {
@@ -1356,8 +1350,7 @@ static int gru_forward_impl(const float* x, const float* h0, const float* const*
     const float* in = x;
     float* gi = scratch + g.gi;
     if (nl == 2) {                                   // two-layer wavefront (see gru2_fwd_kernel)
-        int rc = D != kH ? in_proj_forward(x, D, params[0], params[2], scratch + g.ipf, gi, B * S, kG, D, st)
-                         : nt_gemm(plain_rows(x, B * S, kH), params[0], kH, params[2], gi, kG, kG, kH, st);
+        int rc = layer_input_projection(0, D, x, params[0], params[2], scratch + g.ipf, gi, B * S, kG, st);
         if (rc) return rc;
         Gru2Fwd p;
         p.x_gi0 = gi;
@@ -1415,10 +1408,9 @@ static int gru_forward_impl(const float* x, const float* h0, const float* const*
         return 0;
     }
     for (int l = 0; l < nl; ++l) {
-        const float* wih = params[4 * l], *whh = params[4 * l + 1], *bih = params[4 * l + 2], *bhh = params[4 * l + 3];
+        const float* whh = params[4 * l + 1], *bhh = params[4 * l + 3];
         float* out = (l == nl - 1) ? y : saved + g.Y[l];
-        int rc = l == 0 && D != kH ? in_proj_forward(x, D, wih, bih, scratch + g.ipf, gi, B * S, kG, D, st)
-                                   : nt_gemm(plain_rows(in, B * S, kH), wih, kH, bih, gi, kG, kG, kH, st);
+        int rc = layer_input_projection(l, D, in, params[4 * l], params[4 * l + 2], scratch + g.ipf, gi, B * S, kG, st);
         if (rc) return rc;
         const float* h0l = h0 ? h0 + (long)l * B * kH : nullptr;
         const dim3 grid(kH / 16, cdiv(B, 16));
@@ -1613,11 +1605,8 @@ static int gru_backward_impl(const float* x, const float* h0, const float* const
                 am[2 * l] = plain_rows(dGi_[l], M, kG);
                 bm[2 * l] = plain_rows(in, M, kH);
                 Cq[2 * l] = grads[4 * l];
-                RowMap hm;                             // h_{t-1} rows: y[b, t-1] (zero row at t = 0; h0 term below)
-                hm.base = yl[l]; hm.R = S; hm.bstride = (long)S * kH; hm.rstride = kH; hm.off = -kH;
-                hm.tmul = 1; hm.tadd = -1; hm.Lin = S; hm.M = M;
                 am[2 * l + 1] = plain_rows(dGh_[l], M, kG);
-                bm[2 * l + 1] = hm;
+                bm[2 * l + 1] = prev_step_rows(yl[l], S, B, kH, false);      // h_{t-1} (zero row at t = 0; h0 term below)
                 Cq[2 * l + 1] = grads[4 * l + 1];
             }
             if (narrow) {                              // dW_ih0 is (3H,D): it leaves the batch, the other three stay in it
@@ -1631,10 +1620,8 @@ static int gru_backward_impl(const float* x, const float* h0, const float* const
         }
         for (int l = 0; l < 2; ++l) {
             if (h0l[l]) {                              // + dGh[:,0,:]^T . h0
-                RowMap g0;
-                g0.base = dGh_[l]; g0.R = 1; g0.bstride = (long)S * kG; g0.rstride = 0; g0.off = 0;
-                g0.tmul = 0; g0.tadd = 0; g0.Lin = 0x7fffffff; g0.M = B;
-                rc = tn_gemm(g0, kG, plain_rows(h0l[l], B, kH), kH, scratch + g.part, grads[4 * l + 1], 1, wst);
+                rc = tn_gemm(first_step_rows(dGh_[l], S, B, kG, false), kG, plain_rows(h0l[l], B, kH), kH, scratch + g.part,
+                             grads[4 * l + 1], 1, wst);
                 if (rc) return rc;
             }
         }
@@ -1643,48 +1630,23 @@ static int gru_backward_impl(const float* x, const float* h0, const float* const
     }
     const float* dYl = dy;
     for (int l = nl - 1; l >= 0; --l) {
-        const float* wih = params[4 * l], *whh = params[4 * l + 1];
-        const float* in = l == 0 ? x : saved + g.Y[l - 1];
-        const float* out = (l == nl - 1) ? y : saved + g.Y[l];
-        const float* h0l = h0 ? h0 + (long)l * B * kH : nullptr;
-        float* dXl = l == 0 ? dx : scratch + g.mid[l & 1];
-        int rc = transpose(whh, whhT, kG, kH, st);       // (3H,H) -> (H,3H)
-        if (rc) return rc;
-        rc = l == 0 && narrow ? 0 : transpose(wih, wihT, kG, kH, st);
+        GradTail t;
+        t.N = kG; t.G = 1; t.T = S; t.R = B; t.D = l == 0 ? D : kH; t.time_major = false;
+        t.dGi = dGi; t.dGh = dGh; t.in = l == 0 ? x : saved + g.Y[l - 1]; t.out = (l == nl - 1) ? y : saved + g.Y[l];
+        t.h0 = h0 ? h0 + (long)l * B * kH : nullptr;
+        t.w = params + 4 * l; t.dw = grads + 4 * l; t.dx = l == 0 ? dx : scratch + g.mid[l & 1];
+        t.whhT = whhT; t.wihT = wihT; t.part = scratch + g.part; t.tmp = scratch + g.tmp; t.ip_scratch = scratch + g.ipb;
+        int rc = tail_transposes(t, st);                 // (3H,H) -> (H,3H)
         if (rc) return rc;
         const dim3 grid(kH / 16, cdiv(B, 16));
-        for (int t = S - 1; t >= 0; --t)
-            hipLaunchKernelGGL(gru_step_bwd_kernel, grid, dim3(256), 0, st, whhT, dYl, out, h0l,
+        for (int s = S - 1; s >= 0; --s)
+            hipLaunchKernelGGL(gru_step_bwd_kernel, grid, dim3(256), 0, st, whhT, dYl, t.out, t.h0,
                                saved + g.R[l], saved + g.Z[l], saved + g.N[l], saved + g.GHN[l], dGi, dGh, DH,
-                               B, S, t);
+                               B, S, s);
         CPC_LAUNCH_CHECK();
-        // weight / bias gradients over all B*S rows
-        const RowMap gim = plain_rows(dGi, M, kG), ghm = plain_rows(dGh, M, kG);
-        rc = l == 0 && narrow ? in_proj_backward(x, D, wih, dGi, scratch + g.ipb, nullptr, grads[0], M, kG, D, st)
-                              : tn_gemm(gim, kG, plain_rows(in, M, kH), kH, scratch + g.part, grads[4 * l], 0, st);
+        rc = tail_gradients(t, st);
         if (rc) return rc;
-        // h_{t-1} rows: y[b, t-1] (zero row at t = 0; the h0 term is added below)
-        RowMap hm;
-        hm.base = out; hm.R = S; hm.bstride = (long)S * kH; hm.rstride = kH; hm.off = -kH;
-        hm.tmul = 1; hm.tadd = -1; hm.Lin = S; hm.M = M;
-        rc = tn_gemm(ghm, kG, hm, kH, scratch + g.part, grads[4 * l + 1], 0, st);
-        if (rc) return rc;
-        if (h0l) {   // + dGh[:,0,:]^T . h0
-            RowMap g0;
-            g0.base = dGh; g0.R = 1; g0.bstride = (long)S * kG; g0.rstride = 0; g0.off = 0;
-            g0.tmul = 0; g0.tadd = 0; g0.Lin = 0x7fffffff; g0.M = B;
-            rc = tn_gemm(g0, kG, plain_rows(h0l, B, kH), kH, scratch + g.part, grads[4 * l + 1], 1, st);
-            if (rc) return rc;
-        }
-        rc = rows_sum(dGi, M, kG, scratch + g.tmp, grads[4 * l + 2], st);
-        if (rc) return rc;
-        rc = rows_sum(dGh, M, kG, scratch + g.tmp, grads[4 * l + 3], st);
-        if (rc) return rc;
-        // dX = dGi . W_ih   (as NT against W_ih^T)
-        rc = l == 0 && narrow ? in_proj_backward(x, D, wih, dGi, scratch + g.ipb, dx, nullptr, M, kG, D, st)
-                              : nt_gemm(gim, wihT, kG, nullptr, dXl, kH, kH, kG, st);
-        if (rc) return rc;
-        dYl = dXl;
+        dYl = t.dx;
     }
     return 0;
 }

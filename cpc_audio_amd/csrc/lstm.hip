@@ -24,10 +24,14 @@
 //   * G heads (cpc_lstm_group_*: the criterion's --rnnMode LSTM predictors, cpc/criterion/criterion.py:66-68 -- K one-layer
 //     LSTMs reading the same context) lie side by side in the columns of every (B,S,.) array and ride in blockIdx.z of the same
 //     four kernels: one GEMM projects the input for all heads, as many whole heads as can be resident share a persistent launch.
+//   * the host side is one layout and one forward / backward for both forms -- one head of nl layers, G heads of one layer
+//     (`heads`, lstm_layout) -- and what stands around the kernels (input projection, the gradients behind the backward
+//     recurrence, persistent or per-step launches) is recurrent_host.h's, shared with gru.hip and rnn.hip.
 #include "cpc_common.h"
 #include "cpc_internal.h"
 #include "gemm_tile.h"
 #include "persist.h"
+#include "recurrent_host.h"
 
 namespace cpc {
 
@@ -117,7 +121,7 @@ __device__ __forceinline__ void lstm_load_h(float4 (&a)[4], const LstmFwd& p, in
         a[ii] = ok && src ? *reinterpret_cast<const float4*>(src + koff + 16 * ii) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// grid = (H/16, ceil(B/16), heads), 256 threads; every workgroup resident at once (lstm_heads_per_launch)
+// grid = (H/16, ceil(B/16), heads), 256 threads; every workgroup resident at once (recur_launch)
 __global__ __launch_bounds__(256) void lstm_persist_fwd_kernel(LstmFwd p, int spin_limit) {
     __shared__ float part[4][4][256];
     lstm_fwd_head(p);
@@ -311,90 +315,51 @@ struct LstmLayout {
     long ipf, ipb;        // D != 256: in_proj.hip's scratch behind the forward's / the backward's (the totals include it)
 };
 
-// D: the input width of layer 0 (cpc_lstm_*_in); at 256 the layout is the one cpc_lstm_layout has always reported
-static bool lstm_layout(int B, int S, int nl, LstmLayout& g, int D = kLH) {
-    if (B <= 0 || S <= 0 || nl <= 0 || nl > 8) return false;
-    if (D < 1 || D > kInProjMaxD) return false;
-    if ((long)B * S > (1L << 21)) return false;          // B*S*4H floats stay below 2^31 (int GEMM rows and offsets)
-    const long bsh = align64l((long)B * S * kLH), bsg = align64l((long)B * S * kLG);
+// G heads side by side in the columns of every (B,S,.) array.  heads: the grouped form (cpc_lstm_group_*) -- one layer at
+// D = 256, no carried or final state, and no mid[] in its scratch; otherwise one head, nl layers, and D the input width of
+// layer 0 (cpc_lstm_*_in; at 256 the layout is the one cpc_lstm_layout has always reported, mid[] at nl = 1 included).
+static bool lstm_layout(int B, int S, int G, int nl, bool heads, LstmLayout& g, int D = kLH) {
+    if (B <= 0 || S <= 0 || G <= 0 || G > 64 || nl <= 0 || nl > 8) return false;
+    if (D < 1 || D > kInProjMaxD || (heads ? nl != 1 || D != kLH : G != 1)) return false;
+    if ((long)B * S > (1L << 21) || (long)B * S * G > (1L << 21)) return false;     // B*S*G*4H floats stay below 2^31
+    const long M = (long)B * S, mh = align64l(M * G * kLH), mg = align64l(M * G * kLG);
     long o = 0;
     for (int l = 0; l < nl; ++l) {
-        g.G[l] = o; o += bsg;
-        g.C[l] = o; o += bsh;
+        g.G[l] = o; o += mg;
+        g.C[l] = o; o += mh;
         g.Y[l] = -1;
-        if (l < nl - 1) { g.Y[l] = o; o += bsh; }
+        if (l < nl - 1) { g.Y[l] = o; o += mh; }
     }
     g.saved_total = o;
     g.gx = 0;
-    g.fwd_total = bsg;
-    o = 0;
-    g.whhT = o; o += (long)kLH * kLG;
-    g.wihT = o; o += (long)kLH * kLG;
-    g.dG = o; o += bsg;
-    g.DC = o; o += align64l((long)B * kLH);
-    g.mid[0] = o; o += bsh;
-    g.mid[1] = o; o += bsh;
-    g.part = o; o += align64l(tn_gemm_part_floats(B * S, kLG, kLH));
-    g.tmp = o; o += align64l((long)kRowsSumGroups * kLG);
-    g.bwd_total = o;
-    g.ipf = g.fwd_total; g.ipb = g.bwd_total;
-    if (D != kLH) {
-        g.fwd_total += in_proj_w_floats(kLG, D);
-        g.bwd_total += in_proj_scratch_floats((long)B * S, kLG, D);
-    }
-    return true;
-}
-
-// How many whole heads (16 * ceil(B/16) workgroups each) of the persistent kernel can be resident at once?  0: not even one.
-// The occupancy query is advisory and can over-report by one block, and more than 4 blocks of 256 threads per CU are not
-// counted on: resident workgroups = CUs * max(1, min(query - 1, 4)).
-template <class K>
-static int lstm_heads_per_launch(K kernel, int B) {
-    int dev = 0, cus = 0, occ = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, 256, 0) != hipSuccess) return 0;
-    const int per_cu = occ - 1 > 4 ? 4 : (occ - 1 < 1 ? 1 : occ - 1);
-    const long fit = (long)cus * per_cu / (16L * cdiv(B, 16));
-    return fit > 64 ? 64 : (int)fit;
-}
-template <class K>
-static bool lstm_persist_fits(K kernel, int B) { return lstm_heads_per_launch(kernel, B) >= 1; }
-
-// The grouped recurrence (cpc_lstm_group_*): every (B,S,.) array holds the G heads side by side
-struct LstmGroupLayout {
-    long G, C, saved_total;
-    long gx, fwd_total;
-    long whhT, wihT, dG, DC, part, tmp, bwd_total;
-};
-
-static bool lstm_group_layout(int B, int S, int G, LstmGroupLayout& g) {
-    if (B <= 0 || S <= 0 || G <= 0 || G > 64) return false;
-    if ((long)B * S > (1L << 21) || (long)B * S * G > (1L << 21)) return false;     // B*S*G*4H floats stay below 2^31
-    const long M = (long)B * S;
-    long o = 0;
-    g.G = o; o += align64l(M * G * kLG);
-    g.C = o; o += align64l(M * G * kLH);
-    g.saved_total = o;
-    g.gx = 0;
-    g.fwd_total = align64l(M * G * kLG);
+    g.fwd_total = mg;
     o = 0;
     g.whhT = o; o += (long)G * kLH * kLG;
     g.wihT = o; o += (long)G * kLH * kLG;
-    g.dG = o; o += align64l(M * G * kLG);
+    g.dG = o; o += mg;
     g.DC = o; o += align64l((long)G * B * kLH);
+    g.mid[0] = o; o += heads ? 0 : mh;
+    g.mid[1] = o; o += heads ? 0 : mh;
     const long pa = tn_gemm_part_floats((int)M, G * kLG, kLH), pb = (long)G * tn_gemm_part_floats((int)M, kLG, kLH);
     g.part = o; o += align64l(pa > pb ? pa : pb);
     g.tmp = o; o += align64l((long)kRowsSumGroups * G * kLG);
     g.bwd_total = o;
+    g.ipf = g.fwd_total; g.ipb = g.bwd_total;
+    if (D != kLH) {
+        g.fwd_total += in_proj_w_floats(kLG, D);
+        g.bwd_total += in_proj_scratch_floats(M, kLG, D);
+    }
     return true;
 }
 
-static bool lstm_ptrs_ok(const float* const* v, int n) {
-    if (!v) return false;
-    for (int k = 0; k < n; ++k)
-        if (!v[k]) return false;
-    return true;
+// The S steps of one layer's recurrence (all G heads, 16 * ceil(B/16) workgroups each)
+static int lstm_recur(const LstmFwd& p, int per_step, hipStream_t st) {
+    return recur_launch(lstm_persist_fwd_kernel, lstm_step_fwd_kernel, p, dim3(kLH / 16, cdiv(p.B, 16)), p.ng, p.S, false, per_step,
+                        p.y, (size_t)p.B * p.S * p.hs, kLstmSpinLimit, st);
+}
+static int lstm_recur(const LstmBwd& p, int per_step, hipStream_t st) {
+    return recur_launch(lstm_persist_bwd_kernel, lstm_step_bwd_kernel, p, dim3(kLH / 16, cdiv(p.B, 16)), p.ng, p.S, true, per_step,
+                        p.dG, (size_t)p.B * p.S * p.gs, kLstmSpinLimit, st);
 }
 
 int lstm_error_flag_fetch(int clear, unsigned* out) { return device_flag_fetch(HIP_SYMBOL(g_lstm_poll_timeout), clear, out); }
@@ -403,56 +368,39 @@ int lstm_error_flag_fetch(int clear, unsigned* out) { return device_flag_fetch(H
 
 using namespace cpc;
 
-extern "C" int cpc_lstm_layout(int B, int S, int nl, long* sizes) {
-    LstmLayout g;
-    CPC_RETURN_IF(!lstm_layout(B, S, nl, g), CPC_ERR_SHAPE);
-    CPC_RETURN_IF(!sizes, CPC_ERR_ARG);
-    sizes[0] = g.saved_total; sizes[1] = g.fwd_total; sizes[2] = g.bwd_total;
-    return 0;
-}
-
 extern "C" int cpc_lstm_layout_in(int B, int S, int nl, int D, long* sizes) {
     LstmLayout g;
-    CPC_RETURN_IF(!lstm_layout(B, S, nl, g, D), CPC_ERR_SHAPE);
-    CPC_RETURN_IF(!sizes, CPC_ERR_ARG);
-    sizes[0] = g.saved_total; sizes[1] = g.fwd_total; sizes[2] = g.bwd_total;
-    return 0;
+    return layout_sizes(lstm_layout(B, S, 1, nl, false, g, D), g, sizes);
 }
 
-// D: x is (B,S,D) and weight_ih_l0 (4H,D); D == 256 is cpc_lstm_forward itself
+extern "C" int cpc_lstm_layout(int B, int S, int nl, long* sizes) { return cpc_lstm_layout_in(B, S, nl, kLH, sizes); }
+
+// D: x is (B,S,D) and weight_ih_l0 (4H,D); D == 256 is cpc_lstm_forward itself.  heads: see lstm_layout.
 static int lstm_forward_impl(const float* x, const float* h0, const float* c0, const float* const* params, float* saved,
-                             float* scratch, float* y, float* hN, float* cN, int B, int S, int nl, int D, int flags, void* stream) {
+                             float* scratch, float* y, float* hN, float* cN, int B, int S, int G, int nl, bool heads, int D,
+                             int flags, void* stream) {
     LstmLayout g;
-    CPC_RETURN_IF(!lstm_layout(B, S, nl, g, D), CPC_ERR_SHAPE);
+    CPC_RETURN_IF(!lstm_layout(B, S, G, nl, heads, g, D), CPC_ERR_SHAPE);
     CPC_RETURN_IF(flags & ~CPC_LSTM_PER_STEP, CPC_ERR_ARG);
-    CPC_RETURN_IF(!x || !lstm_ptrs_ok(params, 4 * nl) || !saved || !scratch || !y || !hN || !cN, CPC_ERR_ARG);
+    CPC_RETURN_IF(!x || !ptrs_ok(params, 4 * nl) || !saved || !scratch || !y || (!heads && (!hN || !cN)), CPC_ERR_ARG);
     CPC_RETURN_IF((h0 == nullptr) != (c0 == nullptr), CPC_ERR_ARG);
     hipStream_t st = (hipStream_t)stream;
-    const int M = B * S;
-    const bool persist = !(flags & CPC_LSTM_PER_STEP) && lstm_persist_fits(lstm_persist_fwd_kernel, B);
-    const dim3 grid(kLH / 16, cdiv(B, 16));
     float* gx = scratch + g.gx;
     const float* in = x;
     for (int l = 0; l < nl; ++l) {
-        const float* wih = params[4 * l], *bih = params[4 * l + 2];
         float* out = l == nl - 1 ? y : saved + g.Y[l];
-        int rc = l == 0 && D != kLH ? in_proj_forward(x, D, wih, bih, scratch + g.ipf, gx, M, kLG, D, st)
-                                    : nt_gemm(plain_rows(in, M, kLH), wih, kLH, bih, gx, kLG, kLG, kLH, st);
+        int rc = layer_input_projection(l, D, in, params[4 * l], params[4 * l + 2], scratch + g.ipf, gx, B * S, G * kLG, st);
         if (rc) return rc;
         LstmFwd p;
         p.gx = gx; p.whh = params[4 * l + 1]; p.bhh = params[4 * l + 3];
         p.h0 = h0 ? h0 + (long)l * B * kLH : nullptr;
         p.c0 = c0 ? c0 + (long)l * B * kLH : nullptr;
         p.y = out; p.G = saved + g.G[l]; p.C = saved + g.C[l];
-        p.hN = hN + (long)l * B * kLH; p.cN = cN + (long)l * B * kLH;
-        p.B = B; p.S = S; p.ng = 1; p.g0 = 0; p.hs = kLH; p.gs = kLG;
-        if (persist) {
-            if (hipMemsetAsync(out, 0xFF, (size_t)M * kLH * sizeof(float), st) != hipSuccess) return CPC_ERR_ARG;
-            hipLaunchKernelGGL(lstm_persist_fwd_kernel, grid, dim3(256), 0, st, p, kLstmSpinLimit);
-        } else {
-            for (int t = 0; t < S; ++t) hipLaunchKernelGGL(lstm_step_fwd_kernel, grid, dim3(256), 0, st, p, t);
-        }
-        CPC_LAUNCH_CHECK();
+        p.hN = hN ? hN + (long)l * B * kLH : nullptr;
+        p.cN = cN ? cN + (long)l * B * kLH : nullptr;
+        p.B = B; p.S = S; p.ng = G; p.g0 = 0; p.hs = (long)G * kLH; p.gs = (long)G * kLG;
+        rc = lstm_recur(p, flags & CPC_LSTM_PER_STEP, st);
+        if (rc) return rc;
         in = out;
     }
     return 0;
@@ -460,76 +408,46 @@ static int lstm_forward_impl(const float* x, const float* h0, const float* c0, c
 
 extern "C" int cpc_lstm_forward(const float* x, const float* h0, const float* c0, const float* const* params, float* saved,
                                 float* scratch, float* y, float* hN, float* cN, int B, int S, int nl, int flags, void* stream) {
-    return lstm_forward_impl(x, h0, c0, params, saved, scratch, y, hN, cN, B, S, nl, kLH, flags, stream);
+    return lstm_forward_impl(x, h0, c0, params, saved, scratch, y, hN, cN, B, S, 1, nl, false, kLH, flags, stream);
 }
 
 extern "C" int cpc_lstm_forward_in(const float* x, const float* h0, const float* c0, const float* const* params, float* saved,
                                    float* scratch, float* y, float* hN, float* cN, int B, int S, int nl, int D, int flags,
                                    void* stream) {
-    return lstm_forward_impl(x, h0, c0, params, saved, scratch, y, hN, cN, B, S, nl, D, flags, stream);
+    return lstm_forward_impl(x, h0, c0, params, saved, scratch, y, hN, cN, B, S, 1, nl, false, D, flags, stream);
 }
 
 static int lstm_backward_impl(const float* x, const float* h0, const float* c0, const float* const* params, const float* saved,
                               const float* y, const float* dy, float* scratch, float* dx, float* const* grads, int B, int S,
-                              int nl, int D, int flags, void* stream) {
+                              int G, int nl, bool heads, int D, int flags, void* stream) {
     LstmLayout g;
-    CPC_RETURN_IF(!lstm_layout(B, S, nl, g, D), CPC_ERR_SHAPE);
+    CPC_RETURN_IF(!lstm_layout(B, S, G, nl, heads, g, D), CPC_ERR_SHAPE);
     CPC_RETURN_IF(flags & ~CPC_LSTM_PER_STEP, CPC_ERR_ARG);
-    CPC_RETURN_IF(!x || !lstm_ptrs_ok(params, 4 * nl) || !saved || !y || !dy || !scratch || !dx ||
-                  !lstm_ptrs_ok(const_cast<const float* const*>(grads), 4 * nl), CPC_ERR_ARG);
+    CPC_RETURN_IF(!x || !ptrs_ok(params, 4 * nl) || !saved || !y || !dy || !scratch || !dx ||
+                  !ptrs_ok(const_cast<const float* const*>(grads), 4 * nl), CPC_ERR_ARG);
     CPC_RETURN_IF((h0 == nullptr) != (c0 == nullptr), CPC_ERR_ARG);
     hipStream_t st = (hipStream_t)stream;
-    const int M = B * S;
-    const bool persist = !(flags & CPC_LSTM_PER_STEP) && lstm_persist_fits(lstm_persist_bwd_kernel, B);
-    const dim3 grid(kLH / 16, cdiv(B, 16));
-    float* whhT = scratch + g.whhT, *wihT = scratch + g.wihT, *dG = scratch + g.dG;
+    float* dG = scratch + g.dG;
     const float* dYl = dy;
     for (int l = nl - 1; l >= 0; --l) {
-        const float* in = l == 0 ? x : saved + g.Y[l - 1];
-        const float* out = l == nl - 1 ? y : saved + g.Y[l];
-        const float* h0l = h0 ? h0 + (long)l * B * kLH : nullptr;
-        float* dXl = l == 0 ? dx : scratch + g.mid[l & 1];
-        int rc = transpose(params[4 * l + 1], whhT, kLG, kLH, st);      // (4H,H) -> (H,4H)
-        if (rc) return rc;
-        const bool narrow = l == 0 && D != kLH;          // layer 0 at another input width: its three products in in_proj.hip
-        rc = narrow ? 0 : transpose(params[4 * l], wihT, kLG, kLH, st);
+        GradTail t;
+        t.N = kLG; t.G = G; t.T = S; t.R = B; t.D = l == 0 ? D : kLH; t.time_major = false;
+        t.dGi = t.dGh = dG; t.in = l == 0 ? x : saved + g.Y[l - 1]; t.out = l == nl - 1 ? y : saved + g.Y[l];
+        t.h0 = h0 ? h0 + (long)l * B * kLH : nullptr;
+        t.w = params + 4 * l; t.dw = grads + 4 * l; t.dx = l == 0 ? dx : scratch + g.mid[l & 1];
+        t.whhT = scratch + g.whhT; t.wihT = scratch + g.wihT; t.part = scratch + g.part; t.tmp = scratch + g.tmp;
+        t.ip_scratch = scratch + g.ipb;
+        int rc = tail_transposes(t, st);
         if (rc) return rc;
         LstmBwd p;
-        p.whhT = whhT; p.dY = dYl; p.G = saved + g.G[l]; p.C = saved + g.C[l];
+        p.whhT = t.whhT; p.dY = dYl; p.G = saved + g.G[l]; p.C = saved + g.C[l];
         p.c0 = c0 ? c0 + (long)l * B * kLH : nullptr;
-        p.dG = dG; p.DC = scratch + g.DC; p.B = B; p.S = S; p.ng = 1; p.g0 = 0; p.hs = kLH; p.gs = kLG;
-        if (persist) {
-            if (hipMemsetAsync(dG, 0xFF, (size_t)M * kLG * sizeof(float), st) != hipSuccess) return CPC_ERR_ARG;
-            hipLaunchKernelGGL(lstm_persist_bwd_kernel, grid, dim3(256), 0, st, p, kLstmSpinLimit);
-        } else {
-            for (int t = S - 1; t >= 0; --t) hipLaunchKernelGGL(lstm_step_bwd_kernel, grid, dim3(256), 0, st, p, t);
-        }
-        CPC_LAUNCH_CHECK();
-        // weight / bias gradients over all B*S rows: dW_ih = dG^T . in, dW_hh = dG^T . h_{t-1}, db_ih = db_hh = sum dG
-        const RowMap gm = plain_rows(dG, M, kLG);
-        rc = narrow ? in_proj_backward(x, D, params[0], dG, scratch + g.ipb, nullptr, grads[0], M, kLG, D, st)
-                    : tn_gemm(gm, kLG, plain_rows(in, M, kLH), kLH, scratch + g.part, grads[4 * l], 0, st);
+        p.dG = dG; p.DC = scratch + g.DC; p.B = B; p.S = S; p.ng = G; p.g0 = 0; p.hs = (long)G * kLH; p.gs = (long)G * kLG;
+        rc = lstm_recur(p, flags & CPC_LSTM_PER_STEP, st);
         if (rc) return rc;
-        RowMap hm;                                       // h_{t-1} rows: out[b, t-1] (zero row at t = 0; h0 term below)
-        hm.base = out; hm.R = S; hm.bstride = (long)S * kLH; hm.rstride = kLH; hm.off = -kLH;
-        hm.tmul = 1; hm.tadd = -1; hm.Lin = S; hm.M = M;
-        rc = tn_gemm(gm, kLG, hm, kLH, scratch + g.part, grads[4 * l + 1], 0, st);
+        rc = tail_gradients(t, st);
         if (rc) return rc;
-        if (h0l) {                                       // + dG[:,0,:]^T . h0
-            RowMap g0;
-            g0.base = dG; g0.R = 1; g0.bstride = (long)S * kLG; g0.rstride = 0; g0.off = 0;
-            g0.tmul = 0; g0.tadd = 0; g0.Lin = 0x7fffffff; g0.M = B;
-            rc = tn_gemm(g0, kLG, plain_rows(h0l, B, kLH), kLH, scratch + g.part, grads[4 * l + 1], 1, st);
-            if (rc) return rc;
-        }
-        rc = rows_sum(dG, M, kLG, scratch + g.tmp, grads[4 * l + 2], st);
-        if (rc) return rc;
-        rc = rows_sum(dG, M, kLG, scratch + g.tmp, grads[4 * l + 3], st);
-        if (rc) return rc;
-        rc = narrow ? in_proj_backward(x, D, params[0], dG, scratch + g.ipb, dx, nullptr, M, kLG, D, st)
-                    : nt_gemm(gm, wihT, kLG, nullptr, dXl, kLH, kLH, kLG, st);   // dX = dG . W_ih (as NT against W_ih^T)
-        if (rc) return rc;
-        dYl = dXl;
+        dYl = t.dx;
     }
     return 0;
 }
@@ -537,96 +455,31 @@ static int lstm_backward_impl(const float* x, const float* h0, const float* c0, 
 extern "C" int cpc_lstm_backward(const float* x, const float* h0, const float* c0, const float* const* params, const float* saved,
                                  const float* y, const float* dy, float* scratch, float* dx, float* const* grads, int B, int S,
                                  int nl, int flags, void* stream) {
-    return lstm_backward_impl(x, h0, c0, params, saved, y, dy, scratch, dx, grads, B, S, nl, kLH, flags, stream);
+    return lstm_backward_impl(x, h0, c0, params, saved, y, dy, scratch, dx, grads, B, S, 1, nl, false, kLH, flags, stream);
 }
 
 extern "C" int cpc_lstm_backward_in(const float* x, const float* h0, const float* c0, const float* const* params,
                                     const float* saved, const float* y, const float* dy, float* scratch, float* dx,
                                     float* const* grads, int B, int S, int nl, int D, int flags, void* stream) {
-    return lstm_backward_impl(x, h0, c0, params, saved, y, dy, scratch, dx, grads, B, S, nl, D, flags, stream);
+    return lstm_backward_impl(x, h0, c0, params, saved, y, dy, scratch, dx, grads, B, S, 1, nl, false, D, flags, stream);
 }
 
 // ---- G heads side by side (the criterion's --rnnMode LSTM predictors): see include/cpc_hip.h
 extern "C" int cpc_lstm_group_layout(int B, int S, int G, long* sizes) {
-    LstmGroupLayout g;
-    CPC_RETURN_IF(!lstm_group_layout(B, S, G, g), CPC_ERR_SHAPE);
-    CPC_RETURN_IF(!sizes, CPC_ERR_ARG);
-    sizes[0] = g.saved_total; sizes[1] = g.fwd_total; sizes[2] = g.bwd_total;
-    return 0;
+    LstmLayout g;
+    return layout_sizes(lstm_layout(B, S, G, 1, true, g), g, sizes);
 }
 
 extern "C" int cpc_lstm_group_forward(const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
                                       float* saved, float* scratch, float* y, int B, int S, int G, int flags, void* stream) {
-    LstmGroupLayout g;
-    CPC_RETURN_IF(!lstm_group_layout(B, S, G, g), CPC_ERR_SHAPE);
-    CPC_RETURN_IF(flags & ~CPC_LSTM_PER_STEP, CPC_ERR_ARG);
-    CPC_RETURN_IF(!x || !w_ih || !w_hh || !b_ih || !b_hh || !saved || !scratch || !y, CPC_ERR_ARG);
-    hipStream_t st = (hipStream_t)stream;
-    const int M = B * S;
-    const int fit = (flags & CPC_LSTM_PER_STEP) ? 0 : lstm_heads_per_launch(lstm_persist_fwd_kernel, B);
-    float* gx = scratch + g.gx;
-    int rc = nt_gemm(plain_rows(x, M, kLH), w_ih, kLH, b_ih, gx, (long)G * kLG, G * kLG, kLH, st);   // all heads' input projection
-    if (rc) return rc;
-    LstmFwd p;
-    p.gx = gx; p.whh = w_hh; p.bhh = b_hh; p.h0 = nullptr; p.c0 = nullptr;
-    p.y = y; p.G = saved + g.G; p.C = saved + g.C; p.hN = nullptr; p.cN = nullptr;
-    p.B = B; p.S = S; p.ng = G; p.g0 = 0; p.hs = (long)G * kLH; p.gs = (long)G * kLG;
-    if (fit >= 1) {
-        if (hipMemsetAsync(y, 0xFF, (size_t)M * G * kLH * sizeof(float), st) != hipSuccess) return CPC_ERR_ARG;
-        for (p.g0 = 0; p.g0 < G; p.g0 += fit)       // as many whole heads per launch as can be resident together
-            hipLaunchKernelGGL(lstm_persist_fwd_kernel, dim3(kLH / 16, cdiv(B, 16), G - p.g0 < fit ? G - p.g0 : fit), dim3(256), 0,
-                               st, p, kLstmSpinLimit);
-    } else {
-        for (int t = 0; t < S; ++t)
-            hipLaunchKernelGGL(lstm_step_fwd_kernel, dim3(kLH / 16, cdiv(B, 16), G), dim3(256), 0, st, p, t);
-    }
-    CPC_LAUNCH_CHECK();
-    return 0;
+    const float* params[4] = {w_ih, w_hh, b_ih, b_hh};
+    return lstm_forward_impl(x, nullptr, nullptr, params, saved, scratch, y, nullptr, nullptr, B, S, G, 1, true, kLH, flags, stream);
 }
 
 extern "C" int cpc_lstm_group_backward(const float* x, const float* w_ih, const float* w_hh, const float* saved, const float* y,
                                        const float* dy, float* scratch, float* dx, float* dw_ih, float* dw_hh, float* db_ih,
                                        float* db_hh, int B, int S, int G, int flags, void* stream) {
-    LstmGroupLayout g;
-    CPC_RETURN_IF(!lstm_group_layout(B, S, G, g), CPC_ERR_SHAPE);
-    CPC_RETURN_IF(flags & ~CPC_LSTM_PER_STEP, CPC_ERR_ARG);
-    CPC_RETURN_IF(!x || !w_ih || !w_hh || !saved || !y || !dy || !scratch || !dx || !dw_ih || !dw_hh || !db_ih || !db_hh,
-                  CPC_ERR_ARG);
-    hipStream_t st = (hipStream_t)stream;
-    const int M = B * S;
-    const int fit = (flags & CPC_LSTM_PER_STEP) ? 0 : lstm_heads_per_launch(lstm_persist_bwd_kernel, B);
-    float* whhT = scratch + g.whhT, *wihT = scratch + g.wihT, *dG = scratch + g.dG;
-    int rc = transpose(w_hh, whhT, kLG, kLH, st, G, (long)kLG * kLH, (long)kLG * kLH);      // per head (4H,H) -> (H,4H)
-    if (rc) return rc;
-    rc = transpose(w_ih, wihT, G * kLG, kLH, st);                                           // stacked (G 4H,H) -> (H,G 4H)
-    if (rc) return rc;
-    LstmBwd p;
-    p.whhT = whhT; p.dY = dy; p.G = saved + g.G; p.C = saved + g.C; p.c0 = nullptr;
-    p.dG = dG; p.DC = scratch + g.DC; p.B = B; p.S = S; p.ng = G; p.g0 = 0; p.hs = (long)G * kLH; p.gs = (long)G * kLG;
-    if (fit >= 1) {
-        if (hipMemsetAsync(dG, 0xFF, (size_t)M * G * kLG * sizeof(float), st) != hipSuccess) return CPC_ERR_ARG;
-        for (p.g0 = 0; p.g0 < G; p.g0 += fit)
-            hipLaunchKernelGGL(lstm_persist_bwd_kernel, dim3(kLH / 16, cdiv(B, 16), G - p.g0 < fit ? G - p.g0 : fit), dim3(256), 0,
-                               st, p, kLstmSpinLimit);
-    } else {
-        for (int t = S - 1; t >= 0; --t)
-            hipLaunchKernelGGL(lstm_step_bwd_kernel, dim3(kLH / 16, cdiv(B, 16), G), dim3(256), 0, st, p, t);
-    }
-    CPC_LAUNCH_CHECK();
-    // stacked dW_ih = dG^T . x and both bias gradients over all heads' gate columns at once; dW_hh head by head in one launch
-    const RowMap gm = plain_rows(dG, M, G * kLG);
-    rc = tn_gemm(gm, G * kLG, plain_rows(x, M, kLH), kLH, scratch + g.part, dw_ih, 0, st);
-    if (rc) return rc;
-    RowMap hm;                                           // h_{t-1} rows of head 0: y[b, t-1, 0:H] (zero row at t = 0)
-    hm.base = y; hm.R = S; hm.bstride = (long)S * G * kLH; hm.rstride = G * kLH; hm.off = -G * kLH;
-    hm.tmul = 1; hm.tadd = -1; hm.Lin = S; hm.M = M;
-    GemmGroup grp;
-    grp.G = G; grp.a = kLG; grp.b = kLH; grp.c = (long)kLG * kLH;
-    rc = tn_gemm(gm, kLG, hm, kLH, scratch + g.part, dw_hh, 0, st, GemmBounds(), grp);
-    if (rc) return rc;
-    rc = rows_sum(dG, M, G * kLG, scratch + g.tmp, db_ih, st);
-    if (rc) return rc;
-    rc = rows_sum(dG, M, G * kLG, scratch + g.tmp, db_hh, st);
-    if (rc) return rc;
-    return nt_gemm(gm, wihT, G * kLG, nullptr, dx, kLH, kLH, G * kLG, st);     // dx = sum over heads of dG_g . W_ih,g
+    const float* params[4] = {w_ih, w_hh, w_ih, w_hh};      // (the backward reads no bias: the two slots only pass the NULL check)
+    float* grads[4] = {dw_ih, dw_hh, db_ih, db_hh};
+    return lstm_backward_impl(x, nullptr, nullptr, params, saved, y, dy, scratch, dx, grads, B, S, G, 1, true, kLH, flags, stream);
 }

@@ -1,4 +1,4 @@
-// Fill-pattern hand-over of the persistent recurrences (gru.hip, lstm.hip).
+// Fill-pattern hand-over of the persistent recurrences (gru.hip, lstm.hip, rnn.hip).
 //
 // A persistent launch runs all S steps of a recurrence; a workgroup takes the values other workgroups produced in the
 // previous step straight from the arrays they are written to.  The host fills those arrays with 0xFFFFFFFF (a NaN payload

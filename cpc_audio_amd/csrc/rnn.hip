@@ -18,11 +18,14 @@
 //     through the fill pattern; y is the only saved state (plus the lower layers' outputs).  dx, dW_ih, dW_hh and both bias
 //     gradients are batched GEMMs / reductions over the T * R rows afterwards;
 //   * per-step kernels (one launch per step for all heads, same MFMAs and summation order -- bit-identical) serve grids of which
-//     not even one head can be resident, and the CPC_RNN_PER_STEP flag.
+//     not even one head can be resident, and the CPC_RNN_PER_STEP flag;
+//   * the host code around the kernels -- input projection, launch choice, the gradients behind the backward recurrence -- is
+//     recurrent_host.h's, shared with gru.hip and lstm.hip.
 #include "cpc_common.h"
 #include "cpc_internal.h"
 #include "gemm_tile.h"
 #include "persist.h"
+#include "recurrent_host.h"
 
 namespace cpc {
 
@@ -107,7 +110,7 @@ __device__ __forceinline__ void rnn_load_prev(float4 (&a)[4], const RnnRec& p, i
         a[ii] = ok && src ? *reinterpret_cast<const float4*>(src + koff + 16 * ii) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// grid = (H/64, ceil(R/16), heads), 256 threads; every workgroup resident at once (rnn_heads_per_launch)
+// grid = (H/64, ceil(R/16), heads), 256 threads; every workgroup resident at once (recur_launch)
 template <bool BWD>
 __global__ __launch_bounds__(256) void rnn_persist_kernel(RnnRec p, int spin_limit) {
     __shared__ float part[4][4][256];
@@ -215,44 +218,11 @@ static bool rnn_layout(int T, int R, int G, int nl, RnnLayout& g, int D = kRH) {
     return true;
 }
 
-// How many whole heads (4 * ceil(R/16) workgroups each) of a persistent kernel can be resident at once?  0: not even one.
-// Resident workgroups are counted as CUs * max(1, min(occupancy query - 1, 4)): the query is advisory and can over-report by one
-// block, and more than 4 blocks of 256 threads per CU are not counted on.
-template <class K>
-static int rnn_heads_per_launch(K kernel, int R) {
-    int dev = 0, cus = 0, occ = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, 256, 0) != hipSuccess) return 0;
-    const int per_cu = occ - 1 > 4 ? 4 : (occ - 1 < 1 ? 1 : occ - 1);
-    const long fit = (long)cus * per_cu / ((long)(kRH / kRU) * cdiv(R, 16));
-    return fit > 64 ? 64 : (int)fit;
-}
-
-// The T steps of one layer's recurrence (all G heads) in either direction
+// The T steps of one layer's recurrence (all G heads, 4 * ceil(R/16) workgroups each) in either direction
 template <bool BWD>
-static int rnn_recur(RnnRec p, int G, int per_step, hipStream_t st) {
-    const int tiles = cdiv(p.R, 16);
-    const int fit = per_step ? 0 : rnn_heads_per_launch(rnn_persist_kernel<BWD>, p.R);
-    if (fit >= 1) {
-        if (hipMemsetAsync(p.out, 0xFF, (size_t)p.T * p.R * p.hs * sizeof(float), st) != hipSuccess) return CPC_ERR_ARG;
-        for (p.g0 = 0; p.g0 < G; p.g0 += fit)
-            hipLaunchKernelGGL(rnn_persist_kernel<BWD>, dim3(kRH / kRU, tiles, G - p.g0 < fit ? G - p.g0 : fit), dim3(256), 0, st, p,
-                               kRnnSpinLimit);
-    } else {
-        p.g0 = 0;
-        for (int q = 0; q < p.T; ++q)
-            hipLaunchKernelGGL(rnn_step_kernel<BWD>, dim3(kRH / kRU, tiles, G), dim3(256), 0, st, p, BWD ? p.T - 1 - q : q);
-    }
-    CPC_LAUNCH_CHECK();
-    return 0;
-}
-
-static bool rnn_ptrs_ok(const float* const* v, int n) {
-    if (!v) return false;
-    for (int k = 0; k < n; ++k)
-        if (!v[k]) return false;
-    return true;
+static int rnn_recur(const RnnRec& p, int G, int per_step, hipStream_t st) {
+    return recur_launch(rnn_persist_kernel<BWD>, rnn_step_kernel<BWD>, p, dim3(kRH / kRU, cdiv(p.R, 16)), G, p.T, BWD, per_step, p.out,
+                        (size_t)p.T * p.R * p.hs, kRnnSpinLimit, st);
 }
 
 int rnn_error_flag_fetch(int clear, unsigned* out) { return device_flag_fetch(HIP_SYMBOL(g_rnn_poll_timeout), clear, out); }
@@ -263,18 +233,12 @@ using namespace cpc;
 
 extern "C" int cpc_rnn_layout(int T, int R, int G, int nl, long* sizes) {
     RnnLayout g;
-    CPC_RETURN_IF(!rnn_layout(T, R, G, nl, g), CPC_ERR_SHAPE);
-    CPC_RETURN_IF(!sizes, CPC_ERR_ARG);
-    sizes[0] = g.saved_total; sizes[1] = g.fwd_total; sizes[2] = g.bwd_total;
-    return 0;
+    return layout_sizes(rnn_layout(T, R, G, nl, g), g, sizes);
 }
 
 extern "C" int cpc_rnn_layout_in(int T, int R, int nl, int D, long* sizes) {
     RnnLayout g;
-    CPC_RETURN_IF(!rnn_layout(T, R, 1, nl, g, D), CPC_ERR_SHAPE);
-    CPC_RETURN_IF(!sizes, CPC_ERR_ARG);
-    sizes[0] = g.saved_total; sizes[1] = g.fwd_total; sizes[2] = g.bwd_total;
-    return 0;
+    return layout_sizes(rnn_layout(T, R, 1, nl, g, D), g, sizes);
 }
 
 // D: x is (.,.,D) and weight_ih_l0 (H,D), one head, either layout (the projection works row by row); D == 256 is cpc_rnn_forward itself
@@ -283,7 +247,7 @@ static int rnn_forward_impl(const float* x, const float* h0, const float* const*
     RnnLayout g;
     CPC_RETURN_IF(!rnn_layout(T, R, G, nl, g, D), CPC_ERR_SHAPE);
     CPC_RETURN_IF(flags & ~(CPC_RNN_PER_STEP | CPC_RNN_TIME_MAJOR), CPC_ERR_ARG);
-    CPC_RETURN_IF(!x || !rnn_ptrs_ok(params, 4 * nl) || !saved || !scratch || !y, CPC_ERR_ARG);
+    CPC_RETURN_IF(!x || !ptrs_ok(params, 4 * nl) || !saved || !scratch || !y, CPC_ERR_ARG);
     CPC_RETURN_IF(G > 1 && (h0 || hN), CPC_ERR_ARG);                     // carried and final state exist for one head only
     hipStream_t st = (hipStream_t)stream;
     const int M = T * R;
@@ -292,9 +256,7 @@ static int rnn_forward_impl(const float* x, const float* h0, const float* const*
     const float* in = x;
     for (int l = 0; l < nl; ++l) {
         float* out = l == nl - 1 ? y : saved + g.Y[l];
-        int rc = l == 0 && D != kRH
-                     ? in_proj_forward(x, D, params[0], params[2], scratch + g.ipf, gx, M, kRH, D, st)
-                     : nt_gemm(plain_rows(in, M, kRH), params[4 * l], kRH, params[4 * l + 2], gx, (long)G * kRH, G * kRH, kRH, st);
+        int rc = layer_input_projection(l, D, in, params[4 * l], params[4 * l + 2], scratch + g.ipf, gx, M, G * kRH, st);
         if (rc) return rc;
         RnnRec p;
         p.w = params[4 * l + 1]; p.add = gx; p.bias = params[4 * l + 3];
@@ -324,59 +286,32 @@ static int rnn_backward_impl(const float* x, const float* h0, const float* const
     RnnLayout g;
     CPC_RETURN_IF(!rnn_layout(T, R, G, nl, g, D), CPC_ERR_SHAPE);
     CPC_RETURN_IF(flags & ~(CPC_RNN_PER_STEP | CPC_RNN_TIME_MAJOR), CPC_ERR_ARG);
-    CPC_RETURN_IF(!x || !rnn_ptrs_ok(params, 4 * nl) || !saved || !y || !dy || !scratch || !dx ||
-                  !rnn_ptrs_ok(const_cast<const float* const*>(grads), 4 * nl), CPC_ERR_ARG);
+    CPC_RETURN_IF(!x || !ptrs_ok(params, 4 * nl) || !saved || !y || !dy || !scratch || !dx ||
+                  !ptrs_ok(const_cast<const float* const*>(grads), 4 * nl), CPC_ERR_ARG);
     CPC_RETURN_IF(G > 1 && h0, CPC_ERR_ARG);
     hipStream_t st = (hipStream_t)stream;
-    const int M = T * R;
     const bool tm = flags & CPC_RNN_TIME_MAJOR;
-    const int tsr = tm ? R : 1, rsr = tm ? 1 : T;
-    const long hs = (long)G * kRH;
-    float* whhT = scratch + g.whhT, *wihT = scratch + g.wihT, *dP = scratch + g.dP;
+    float* dP = scratch + g.dP;
     const float* dYl = dy;
     for (int l = nl - 1; l >= 0; --l) {
-        const float* in = l == 0 ? x : saved + g.Y[l - 1];
         const float* out = l == nl - 1 ? y : saved + g.Y[l];
-        const float* h0l = h0 ? h0 + (long)l * R * kRH : nullptr;
-        float* dXl = l == 0 ? dx : scratch + g.mid[l & 1];
-        int rc = transpose(params[4 * l + 1], whhT, kRH, kRH, st, G, (long)kRH * kRH, (long)kRH * kRH);   // per head
-        if (rc) return rc;
-        const bool narrow = l == 0 && D != kRH;          // layer 0 at another input width: its three products in in_proj.hip
-        rc = narrow ? 0 : transpose(params[4 * l], wihT, G * kRH, kRH, st);   // stacked (G H,H) -> (H,G H)
+        GradTail t;
+        t.N = kRH; t.G = G; t.T = T; t.R = R; t.D = l == 0 ? D : kRH; t.time_major = tm;
+        t.dGi = t.dGh = dP; t.in = l == 0 ? x : saved + g.Y[l - 1]; t.out = out;
+        t.h0 = h0 ? h0 + (long)l * R * kRH : nullptr;
+        t.w = params + 4 * l; t.dw = grads + 4 * l; t.dx = l == 0 ? dx : scratch + g.mid[l & 1];
+        t.whhT = scratch + g.whhT; t.wihT = scratch + g.wihT; t.part = scratch + g.part; t.tmp = scratch + g.tmp;
+        t.ip_scratch = scratch + g.ipb;
+        int rc = tail_transposes(t, st);
         if (rc) return rc;
         RnnRec p;
-        p.w = whhT; p.add = dYl; p.bias = nullptr; p.first = nullptr; p.yv = out; p.out = dP; p.last = nullptr;
-        p.T = T; p.R = R; p.tsr = tsr; p.rsr = rsr; p.g0 = 0; p.hs = hs;
+        p.w = t.whhT; p.add = dYl; p.bias = nullptr; p.first = nullptr; p.yv = out; p.out = dP; p.last = nullptr;
+        p.T = T; p.R = R; p.tsr = tm ? R : 1; p.rsr = tm ? 1 : T; p.g0 = 0; p.hs = (long)G * kRH;
         rc = rnn_recur<true>(p, G, flags & CPC_RNN_PER_STEP, st);
         if (rc) return rc;
-        // over all T*R rows: stacked dW_ih = dP^T . in, dW_hh = dP^T . h_{t-1} head by head in one launch, db_ih = db_hh = sum dP
-        const RowMap gm = plain_rows(dP, M, G * kRH);
-        rc = narrow ? in_proj_backward(x, D, params[0], dP, scratch + g.ipb, nullptr, grads[0], M, kRH, D, st)
-                    : tn_gemm(gm, G * kRH, plain_rows(in, M, kRH), kRH, scratch + g.part, grads[4 * l], 0, st);
+        rc = tail_gradients(t, st);
         if (rc) return rc;
-        RowMap hm;                                       // h_{t-1} rows of head 0 (zero rows at t = 0; h0 term below)
-        hm.base = out; hm.rstride = (int)hs; hm.tmul = 1; hm.M = M;
-        if (tm) { hm.R = M; hm.bstride = 0; hm.off = -(int)(R * hs); hm.tadd = -R; hm.Lin = M; }
-        else { hm.R = T; hm.bstride = (long)T * hs; hm.off = -(int)hs; hm.tadd = -1; hm.Lin = T; }
-        GemmGroup grp;
-        grp.G = G; grp.a = kRH; grp.b = kRH; grp.c = (long)kRH * kRH;
-        rc = tn_gemm(gm, kRH, hm, kRH, scratch + g.part, grads[4 * l + 1], 0, st, GemmBounds(), grp);
-        if (rc) return rc;
-        if (h0l) {                                       // + dP[t = 0]^T . h0
-            RowMap g0;
-            g0.base = dP; g0.R = 1; g0.bstride = (long)rsr * hs; g0.rstride = 0; g0.off = 0;
-            g0.tmul = 0; g0.tadd = 0; g0.Lin = 0x7fffffff; g0.M = R;
-            rc = tn_gemm(g0, kRH, plain_rows(h0l, R, kRH), kRH, scratch + g.part, grads[4 * l + 1], 1, st);
-            if (rc) return rc;
-        }
-        rc = rows_sum(dP, M, G * kRH, scratch + g.tmp, grads[4 * l + 2], st);
-        if (rc) return rc;
-        rc = rows_sum(dP, M, G * kRH, scratch + g.tmp, grads[4 * l + 3], st);
-        if (rc) return rc;
-        rc = narrow ? in_proj_backward(x, D, params[0], dP, scratch + g.ipb, dx, nullptr, M, kRH, D, st)
-                    : nt_gemm(gm, wihT, G * kRH, nullptr, dXl, kRH, kRH, G * kRH, st);     // dX = dP . W_ih, summed over the heads
-        if (rc) return rc;
-        dYl = dXl;
+        dYl = t.dx;
     }
     return 0;
 }

@@ -245,7 +245,7 @@ def test_cells_match_torch_float64_at_other_input_widths_emulated(cell, D, B, S,
     assert lib.cpc_device_error_flags(1) == 0
 
 
-@pytest.mark.parametrize("cell,B,S,nl,D,use_state", [("gru", 5, 7, 2, 40, False), ("gru", 20, 9, 2, 13, True),
+@pytest.mark.parametrize("cell,B,S,nl,D,use_state", [("gru", 5, 7, 2, 40, False), ("gru", 20, 9, 2, 13, True), ("gru", 3, 4, 3, 40, True),
                                                      ("lstm", 5, 7, 1, 40, False), ("lstm", 20, 9, 2, 512, True),
                                                      ("rnn", 5, 7, 1, 13, True), ("rnn", 20, 9, 2, 40, False)])
 def test_persistent_and_per_step_paths_agree_bit_for_bit_emulated(cell, B, S, nl, D, use_state):
