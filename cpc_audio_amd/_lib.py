@@ -83,6 +83,8 @@ SIGNATURES = {
     "cpc_conv_layer_wgrad": (_I, [_P] * 6 + [_I] * 7 + [_P]),
     "cpc_encoder_layout": (_I, [_I, _I, _P]),
     "cpc_encoder_saved_activation": (_I, [_P, _I, _P, _I, _I, _P]),
+    "cpc_encoder_backward_offsets": (_I, [_I, _I, _P]),
+    "cpc_encoder_keep_data_gradients": (_I, [_P]),
     "cpc_encoder_forward": (_I, [_P] * 5 + [_I, _I, _P]),
     "cpc_encoder_prepare_weights": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "cpc_encoder_backward": (_I, [_P] * 7 + [_I, _I, _P]),

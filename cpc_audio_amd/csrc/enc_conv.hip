@@ -384,6 +384,10 @@ constexpr int NB_ROWS = 32;   // rows per block (8 per wave)
 // MASK: where [y > 0] comes from.  0: y in fp32; 1: y in H2 storage (cpc_common.h; the sign of the h piece is the value's);
 // 2: recomputed as fmaf(xhat, w, b) > 0 -- the very expression the forward kernels rectify, on the very xhat they stored,
 // so the mask is bit-identical and the 4 bytes per element of y are not read at all (the composite encoder's choice).
+// (XB, the bf16-storage variant, is the exception: its forward rectifies fmaf(xh, w, b) on the UNROUNDED xh and stores
+// bf16(xh), which is what this kernel sees.  The two masks differ where the rounding of xh moves the pre-activation across
+// zero: only where |xh w + b| <= 2^-8 |xh w|, a share of ~1e-4 of a layer's elements, whose y is within that band of zero --
+// accepted as part of the variant and held to that band by tests/test_*_bf16_rounding.py; DESIGN.md, the bf16-storage section.)
 // The kernel streams 12-16 bytes per element and is latency-bound per row (two dependent wave reductions), so a wave
 // keeps the loads of four rows in flight and interleaves their reduction chains (0.25 -> ... ms per step for the four layers).
 // DYB / XB: dy / (xhat and the output dx) are bf16 tensors (the bf16-storage variant, mode 4) instead of fp32.
@@ -1270,6 +1274,14 @@ extern "C" int cpc_set_h2_dx(int on) {
     g_wgrad_dma = on == 2 ? 0 : 1;            // 2: H2 gradient, but its weight gradient on the register-staged TN tile (A/B)
     return 0;
 }
+// Tests / debugging, bf16 storage (mode 4) only: the data gradients of layers 2..4 go through ONE temporary (EncLayout::dy0) that
+// the next layer's overwrites.  With a buffer set here, cpc_encoder_backward copies each of them out before its norm backward reads
+// it: dy1, dy2, dy3 -- the gradients w.r.t. y1, y2, y3, bf16 (B, L_i, 256) -- back to back.  nullptr (default): no copies.
+static void* g_keep_dy = nullptr;
+extern "C" int cpc_encoder_keep_data_gradients(void* buf) {
+    g_keep_dy = buf;
+    return 0;
+}
 extern "C" int cpc_set_h2_layers(int n) {
     CPC_RETURN_IF(n < 0 || n == 3 || n > 4, CPC_ERR_ARG);
     g_h2_layers = n;
@@ -1508,6 +1520,19 @@ extern "C" int cpc_encoder_saved_activation(const float* saved, int layer, float
     return 0;
 }
 
+// Where the tensors that survive a cpc_encoder_backward lie in its scratch: offs[0..3] = dx1..dx4, the gradients w.r.t. the
+// conv outputs of layers 1..4 (B, L_i, 256), offs[4] = dy0, the gradient w.r.t. layer 0's output (B, L0, 256) -- offsets in
+// floats, storage as the mode says (mode 4: bf16 elements from that float offset on).  dy0 doubles as the temporary of the upper
+// layers' data gradients: only layer 1's survives.  For tests and debugging; call it in the mode the backward ran in.
+extern "C" int cpc_encoder_backward_offsets(int B, int L, long* offs) {
+    EncLayout e;
+    CPC_RETURN_IF(B <= 0 || !enc_layout(B, L, e), CPC_ERR_SHAPE);
+    CPC_RETURN_IF(!offs, CPC_ERR_ARG);
+    for (int i = 1; i < 5; ++i) offs[i - 1] = e.dx[i];
+    offs[4] = e.dy0;
+    return 0;
+}
+
 // train_step.hip: an event to record on the forward's stream right behind layer 0's launch (the composite step releases the
 // criterion's index preparation there when asked to); per host thread, nullptr = none
 namespace cpc {
@@ -1739,7 +1764,8 @@ static int encoder_backward_impl(const float* wave, const float* const* params, 
     int njobs = 0;
     auto norm_bwd = [&](int layer, const float* dy, const float* yl, float* dxl) {
         const int M = B * e.L[layer], nblk = cdiv(M, NB_ROWS);
-        // the ReLU mask is recomputed from xhat and the affine (bit-identical to the forward's): y is not read
+        // the ReLU mask is recomputed from xhat and the affine (bit-identical to the forward's where xhat is stored in fp32; from
+        // the bf16-rounded xhat in bf16 storage, see norm_bwd_kernel): y is not read
         if (e.bf16 && layer == 4)         // bf16 storage: xhat and dx are bf16; the top layer's dy is autograd's fp32 dz
             hipLaunchKernelGGL((norm_bwd_kernel<2, false, true>), dim3(nblk), dim3(256), 0, st, dy, saved + e.xhat[layer], yl,
                                saved + e.rstd[layer], params[4 * layer + 2], params[4 * layer + 3], dxl, scratch + e.colp[layer],
@@ -1841,6 +1867,13 @@ static int encoder_backward_impl(const float* wave, const float* const* params, 
                                      kGeom[i].s, kGeom[i].p, st);
             if (rc) return rc;
             zero_uncovered_rows(tmpd, B, e.L[i - 1], e.L[i], kGeom[i].s, kGeom[i].p, kC * 2, st);
+            if (i >= 2 && g_keep_dy) {       // tests: this temporary is the next layer's too (cpc_encoder_keep_data_gradients)
+                long off = 0;
+                for (int j = 1; j < i - 1; ++j) off += (long)B * e.L[j] * kC;
+                if (hipMemcpyAsync(reinterpret_cast<unsigned short*>(g_keep_dy) + off, tmpd, (size_t)B * e.L[i - 1] * kC * 2,
+                                   hipMemcpyDeviceToDevice, st) != hipSuccess)
+                    return CPC_ERR_ARG;
+            }
             if (i >= 2) norm_bwd(i - 1, tmpd, xin, scratch + e.dx[i - 1]);
         } else if (i >= 2 && (e.dxh2[i] || e.dxh2[i - 1] || (g_unfuse_big && (g_unfuse_big == 2 || pick_bm(B * (e.L[i] + 1)) == 128)))) {
             // the fused ReLU'/ChannelNorm-backward epilogue is latency-bound (row-by-row reductions between the loads); a

@@ -238,6 +238,14 @@ int cpc_encoder_layout(int B, int L, long* sizes);
 /* fp32 copy of the saved output of layer `layer` (0..3) of a cpc_encoder_forward, whatever its storage: dst (B,L_layer,256).
  * Tests / debugging; call it in the mode the forward ran in. */
 int cpc_encoder_saved_activation(const float* saved, int layer, float* dst, int B, int L, void* stream);
+/* Offsets (in floats, into the backward scratch) of the tensors that survive a cpc_encoder_backward: offs[0..3] = dx1..dx4, the
+ * gradients w.r.t. the conv outputs of layers 1..4 (B,L_i,256), offs[4] = dy0, the gradient w.r.t. layer 0's output (B,L0,256);
+ * stored as the mode says (mode 4: bf16 elements).  Tests / debugging; call it in the mode the backward ran in. */
+int cpc_encoder_backward_offsets(int B, int L, long* offs);
+/* Tests / debugging, mode 4 only: the data gradients of layers 2..4 share one temporary, which the next layer's overwrites.  With a
+ * device buffer set here, cpc_encoder_backward copies each out before its norm backward reads it: dy1, dy2, dy3 (the gradients
+ * w.r.t. y1, y2, y3; bf16 (B,L_i,256)) back to back, B*(L1+L2+L3)*256 bf16 elements.  NULL (default): no copies.  Process-wide. */
+int cpc_encoder_keep_data_gradients(void* buf);
 int cpc_encoder_forward(const float* wave, const float* const* params, float* saved,
                         float* scratch, float* z, int B, int L, void* stream);
 /* The weight-only preparation cpc_encoder_forward starts with (GEMM layouts and max|w| of conv1..4, bounds of the layers'
