@@ -146,6 +146,10 @@ SIGNATURES = {
     "cpc_classifier_backward": (_I, [_P, _L] + [_P] * 9 + [_I, _I, _P]),
     "cpc_ctc_forward": (_I, [_P] * 6 + [_I, _I, _I, _P]),
     "cpc_ctc_backward": (_I, [_P] * 3 + [_I, _I, _I, _P]),
+    "cpc_supervised_layout_d": (_I, [_I, _I, _I, _I, _I, _P]),
+    "cpc_classifier_forward_d": (_I, [_P, _L] + [_P] * 6 + [_I, _I, _I, _P]),
+    "cpc_classifier_backward_d": (_I, [_P, _L] + [_P] * 9 + [_I, _I, _I, _P]),
+    "cpc_ctc_forward_d": (_I, [_P] * 6 + [_I, _I, _I, _I, _P]),
     "cpc_phone_head_layout": (_I, [_I, _I, _I, _I, _P]),
     "cpc_phone_head_forward": (_I, [_P] * 6 + [_I, _I, _I, _P]),
     "cpc_phone_head_backward": (_I, [_P] * 7 + [_I, _I, _I, _P]),
@@ -167,6 +171,9 @@ SIGNATURES = {
     "cpc_probe_layout": (_I, [_I, _I, _P]),
     "cpc_probe_train_step": (_I, [_P, _L, _P, _I, _I] + [_P] * 6 + [ctypes.c_double] * 6 + [_P] * 7),
     "cpc_probe_eval": (_I, [_P, _L, _P, _I, _I] + [_P] * 7),
+    "cpc_probe_layout_d": (_I, [_I, _I, _I, _P]),
+    "cpc_probe_train_step_d": (_I, [_P, _L, _P, _I, _I, _I] + [_P] * 6 + [ctypes.c_double] * 6 + [_P] * 7),
+    "cpc_probe_eval_d": (_I, [_P, _L, _P, _I, _I, _I] + [_P] * 7),
     "cpc_posterior_forward": (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _P, _P]),
     "cpc_abx_layout": (_I, [_I, _I, _I, _L, _P]),
     "cpc_abx_group_scores": (_I, [_P, _P, _P, _I, _L, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P]),

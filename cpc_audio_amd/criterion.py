@@ -536,9 +536,19 @@ class CPCUnsupersivedCriterion(BaseCriterion):
 # train.py --supervised train on top of CPC features.  With 256 input features and one linear layer the loss, the accuracy and
 # every gradient run in csrc/supervised.hip (ops.ClassifierXentFunction / ops.CtcXentFunction: CUDA fp32 only, CPU tensors
 # raise); other widths and nLayers > 1 run on the modules' own torch ops (``hip_path`` is False), as the reference does.
+# ``wideKernel`` (an addition; off by default): one linear layer on 1 to 512 features other than 256 runs the same Functions on the
+# library's _d entry points for CUDA fp32 input (``hip_wide``; ``hip_path`` keeps its value) and the torch ops for anything else.
 
 def _on_hip(layer, dim):
     return dim == 256 and isinstance(layer, nn.Linear)
+
+
+def _on_hip_wide(layer, dim, wideKernel):
+    return bool(wideKernel) and 1 <= dim <= 512 and dim != 256 and isinstance(layer, nn.Linear)
+
+
+def _takes_wide(crit, features):
+    return crit.hip_wide and features.is_cuda and features.dtype == torch.float32
 
 
 class NoneCriterion(BaseCriterion):
@@ -551,18 +561,19 @@ class NoneCriterion(BaseCriterion):
 class SpeakerCriterion(BaseCriterion):
     """cpc/criterion/criterion.py:182-203: a linear classifier of the last frame's context vector."""
 
-    def __init__(self, dimEncoder, nSpeakers):
+    def __init__(self, dimEncoder, nSpeakers, wideKernel=False):
         super().__init__()
         self.linearSpeakerClassifier = nn.Linear(dimEncoder, nSpeakers)
         self.lossCriterion = nn.CrossEntropyLoss()
         self.entropyCriterion = nn.LogSoftmax(dim=1)
         self.hip_path = _on_hip(self.linearSpeakerClassifier, dimEncoder)
+        self.hip_wide = _on_hip_wide(self.linearSpeakerClassifier, dimEncoder, wideKernel)
 
     def forward(self, cFeature, otherEncoded, label):
         batchSize = cFeature.size(0)
         last = cFeature[:, -1, :]                              # read in place by the kernel (row stride S * 256)
         lin = self.linearSpeakerClassifier
-        if self.hip_path:
+        if self.hip_path or _takes_wide(self, last):
             return ClassifierXentFunction.apply(last, label, lin.weight, lin.bias)
         predictions = lin(last.reshape(batchSize, -1))
         loss = self.lossCriterion(predictions, label).view(1, -1)
@@ -574,7 +585,7 @@ class PhoneCriterion(BaseCriterion):
     """cpc/criterion/criterion.py:206-246: a per-frame classifier of the context vectors (or of the encoder's output when
     ``onEncoder``); nLayers > 1 stacks Linear / ReLU / Linear (nPhones wide) and runs on torch."""
 
-    def __init__(self, dimEncoder, nPhones, onEncoder, nLayers=1):
+    def __init__(self, dimEncoder, nPhones, onEncoder, nLayers=1, wideKernel=False):
         super().__init__()
         if nLayers == 1:
             self.PhoneCriterionClassifier = nn.Linear(dimEncoder, nPhones)
@@ -587,13 +598,14 @@ class PhoneCriterion(BaseCriterion):
         self.lossCriterion = nn.CrossEntropyLoss()
         self.onEncoder = onEncoder
         self.hip_path = _on_hip(self.PhoneCriterionClassifier, dimEncoder)
+        self.hip_wide = _on_hip_wide(self.PhoneCriterionClassifier, dimEncoder, wideKernel)
 
     def forward(self, cFeature, otherEncoded, label):
         features = otherEncoded if self.onEncoder else cFeature
         B, S = features.size(0), features.size(1)
         if label.dim() != 2 or tuple(label.shape) != (B, S):
             raise ValueError(f"PhoneCriterion: per-frame labels of shape ({B}, {S}) expected, got {tuple(label.shape)}")
-        if self.hip_path:
+        if self.hip_path or _takes_wide(self, features):
             lin = self.PhoneCriterionClassifier
             return ClassifierXentFunction.apply(features.reshape(B * S, -1), label.reshape(-1), lin.weight, lin.bias)
         predictions = self.getPrediction(features)
@@ -623,7 +635,7 @@ class CTCPhoneCriterion(BaseCriterion):
     """cpc/criterion/criterion.py:249-283: a per-frame classifier with one extra (blank) class trained with nn.CTCLoss on the
     collapsed frame labels; the second output is zeros(1, 1), as in the reference."""
 
-    def __init__(self, dimEncoder, nPhones, onEncoder):
+    def __init__(self, dimEncoder, nPhones, onEncoder, wideKernel=False):
         super().__init__()
         self.PhoneCriterionClassifier = nn.Linear(dimEncoder, nPhones + 1)
         self.lossCriterion = nn.CTCLoss(blank=nPhones, zero_infinity=True)
@@ -632,6 +644,7 @@ class CTCPhoneCriterion(BaseCriterion):
             raise ValueError("On encoder version not implemented yet")
         self.BLANK_LABEL = nPhones
         self.hip_path = _on_hip(self.PhoneCriterionClassifier, dimEncoder)
+        self.hip_wide = _on_hip_wide(self.PhoneCriterionClassifier, dimEncoder, wideKernel)
 
     def getPrediction(self, cFeature):
         B, S, H = cFeature.size()
@@ -642,7 +655,7 @@ class CTCPhoneCriterion(BaseCriterion):
         B, S, H = cFeature.size()
         if label.dim() != 2 or tuple(label.shape) != (B, S):
             raise ValueError(f"CTCPhoneCriterion: per-frame labels of shape ({B}, {S}) expected, got {tuple(label.shape)}")
-        if self.hip_path:
+        if self.hip_path or _takes_wide(self, cFeature):
             lin = self.PhoneCriterionClassifier
             loss = CtcXentFunction.apply(cFeature, label, lin.weight, lin.bias)
             return loss, torch.zeros(1, 1, device=loss.device)

@@ -3,6 +3,8 @@
 // with f32 MFMAs), and a row's softmax statistics (maximum, first index of the maximum, sum of exponentials) from one 64-class
 // step and merged over steps.
 // The loaders take any argument struct with the members they name: x, ldx, R and W, b, C.
+// probe.hip's probe_wide_kernel (any feature width) has loaders and a logits loop of its own at its row pitch and shares
+// probe_merge and probe_row_stats.
 #pragma once
 #include <climits>
 

@@ -2,7 +2,8 @@
 // SpeakerCriterion and PhoneCriterion are, and the CTC loss of CTCPhoneCriterion -- what cpc/eval/linear_separability.py and
 // train.py --supervised train on top of CPC features.
 //
-// Classifier (cpc_classifier_forward / _backward), R rows of 256 features, C classes:
+// Classifier (cpc_classifier_forward / _backward: R rows of 256 features; cpc_classifier_forward_d / _backward_d: of D features,
+// 1 <= D <= 512 -- the same host functions, which take D, on the same kernels), C classes:
 //   logits = x W^T + b                         sup_prod_kernel, 64 x 64 tiles, exact-f32 FMA, masked in rows and classes
 //   lse, argmax, per-row loss / hit            sup_rows_kernel, one wave per row, max / sum-exp over 64-class tiles
 //   loss = mean, acc = mean (float64)          sup_mean_kernel, one workgroup, fixed-order tree
@@ -10,7 +11,7 @@
 //   dW = dlogits^T x, db = sum dlogits         per-slab partial products over row slabs, then sup_slab_sum_kernel adds the
 //                                              slabs in slab order: no float atomics, the same bits on every run
 //   dX = dlogits W                             sup_prod_kernel (only when the caller passes dX)
-// CTC (cpc_ctc_forward / _backward): log_softmax + nn.CTCLoss(blank = C-1, zero_infinity = True, reduction mean) with every
+// CTC (cpc_ctc_forward / cpc_ctc_forward_d / cpc_ctc_backward, which works on the logits and serves every width): log_softmax + nn.CTCLoss(blank = C-1, zero_infinity = True, reduction mean) with every
 // input length S.  ctc_collapse_kernel collapses the frame labels (cpc/criterion/seq_alignment.py:64-86) into padded targets
 // with their lengths, and the loss itself is the library's one CTC loss (ctc_loss.hip) on the product's logits.
 #include <climits>
@@ -25,6 +26,7 @@ constexpr int kSupMaxClasses = 8192;
 constexpr int kCtcMaxSeq = 512;
 constexpr int kSupSlabRows = 256;          // rows per dW / db partial slab (before the caps below)
 constexpr int kSupMaxSlabs = 32;
+constexpr int kSupMaxDim = 512;            // widest feature row of the _d entry points
 
 // Set (bit 0) by a kernel that met a label outside [0, C) (CTC: [0, C-1)); read and cleared by cpc_device_error_flags()
 // (capi.hip) as CPC_DEVERR_LABEL_RANGE.  The label is clamped for addressing and the loss made NaN.
@@ -192,9 +194,9 @@ int head_colsum(const float* dl, float* dbp, int R, int C, int kchunk, int Z, hi
 
 // dW = sum_z part[z], db = sum_z dbp[z], slabs in order
 __global__ __launch_bounds__(256) void sup_slab_sum_kernel(const float* __restrict__ part, const float* __restrict__ dbp,
-                                                           float* __restrict__ dW, float* __restrict__ db, int C, int Z) {
+                                                           float* __restrict__ dW, float* __restrict__ db, int C, int D, int Z) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    const long nw = (long)C * kC;
+    const long nw = (long)C * D;
     if (i < nw) {
         float s = 0.f;
         for (int z = 0; z < Z; ++z) s += part[(long)z * nw + i];
@@ -246,7 +248,9 @@ struct SupLayout {
     int Z, kchunk;
 };
 
-static int sup_layout(int B, int S, int C, int ctc, SupLayout* o) {
+// D features per row, 1 <= D <= kSupMaxDim (the 256 entry points: kC)
+static int sup_layout(int B, int S, int C, int D, int ctc, SupLayout* o) {
+    CPC_RETURN_IF(D < 1 || D > kSupMaxDim, CPC_ERR_SHAPE);
     CPC_RETURN_IF(B < 1 || S < 1 || C < 2 || C > kSupMaxClasses, CPC_ERR_SHAPE);
     CPC_RETURN_IF(ctc && S > kCtcMaxSeq, CPC_ERR_SHAPE);
     const long R = (long)B * S;
@@ -270,40 +274,36 @@ static int sup_layout(int B, int S, int C, int ctc, SupLayout* o) {
     }
     int Z = (int)((R + kSupSlabRows - 1) / kSupSlabRows);
     Z = min(Z, kSupMaxSlabs);
-    Z = min(Z, max(1, (1 << 17) / C));                        // partial slabs stay <= 2^17 x 256 floats
+    Z = (int)min((long)Z, max(1L, (1L << 25) / ((long)C * D)));   // the partial slabs (Z x C x D) stay <= 2^25 floats: 2^17 / C slabs at D = 256
     int kchunk = (int)((R + Z - 1) / Z);
     kchunk = (kchunk + kHK - 1) / kHK * kHK;
     o->kchunk = kchunk;
     o->Z = (int)((R + kchunk - 1) / kchunk);
     o->dl = 0;
     o->part = rc;
-    o->dbp = o->part + align64l((long)o->Z * C * kC);
+    o->dbp = o->part + align64l((long)o->Z * C * D);
     o->scratch = o->dbp + align64l((long)o->Z * C);
     o->dlogits = ctc ? R * C : 0;
     return 0;
 }
 
 static int sup_logits(const float* x, long ldx, const float* W, const float* b, float* saved, const SupLayout& ly, int R, int C,
-                      hipStream_t st) {
+                      int D, hipStream_t st) {
     SupProd p{};
     p.A = x; p.sam = ldx; p.sak = 1;
-    p.B = W; p.sbn = kC; p.sbk = 1;
+    p.B = W; p.sbn = D; p.sbk = 1;
     p.bias = b;
     p.out = saved + ly.logits; p.ldc = C; p.slab = 0;
-    p.M = R; p.N = C; p.K = kC; p.kchunk = kC;
+    p.M = R; p.N = C; p.K = D; p.kchunk = D;
     return sup_prod(p, 1, st);
 }
 
 int sup_error_flag_fetch(int clear, unsigned* out) { return device_flag_fetch(HIP_SYMBOL(g_sup_label_range), clear, out); }
 
-}  // namespace cpc
-
-using namespace cpc;
-
-extern "C" int cpc_supervised_layout(int B, int S, int C, int ctc, long* sizes) {
+static int sup_layout_sizes(int B, int S, int C, int D, int ctc, long* sizes) {
     CPC_RETURN_IF(!sizes || (ctc != 0 && ctc != 1), CPC_ERR_ARG);
     SupLayout ly;
-    const int rc = sup_layout(B, S, C, ctc, &ly);
+    const int rc = sup_layout(B, S, C, D, ctc, &ly);
     if (rc) return rc;
     sizes[0] = ly.saved;
     sizes[1] = ly.scratch;
@@ -311,14 +311,13 @@ extern "C" int cpc_supervised_layout(int B, int S, int C, int ctc, long* sizes) 
     return 0;
 }
 
-extern "C" int cpc_classifier_forward(const float* x, long ldx, const float* W, const float* b, const long long* labels,
-                                      float* saved, float* loss, double* acc, int R, int C, void* stream) {
+static int classifier_forward(const float* x, long ldx, const float* W, const float* b, const long long* labels, float* saved,
+                              float* loss, double* acc, int R, int C, int D, hipStream_t st) {
     SupLayout ly;
-    const int rc = sup_layout(R, 1, C, 0, &ly);
+    const int rc = sup_layout(R, 1, C, D, 0, &ly);
     if (rc) return rc;
-    CPC_RETURN_IF(!x || ldx < kC || !W || !b || !labels || !saved || !loss || !acc, CPC_ERR_ARG);
-    const hipStream_t st = (hipStream_t)stream;
-    const int r2 = sup_logits(x, ldx, W, b, saved, ly, R, C, st);
+    CPC_RETURN_IF(!x || ldx < D || !W || !b || !labels || !saved || !loss || !acc, CPC_ERR_ARG);
+    const int r2 = sup_logits(x, ldx, W, b, saved, ly, R, C, D, st);
     if (r2) return r2;
     hipLaunchKernelGGL(sup_rows_kernel, dim3((R + 3) / 4), dim3(256), 0, st, saved + ly.logits, labels, saved + ly.lse,
                        saved + ly.row_loss, saved + ly.row_hit, R, C);
@@ -328,15 +327,14 @@ extern "C" int cpc_classifier_forward(const float* x, long ldx, const float* W, 
     return 0;
 }
 
-extern "C" int cpc_classifier_backward(const float* x, long ldx, const float* W, const long long* labels, const float* saved,
-                                       const float* dloss, const float* dlogits, float* scratch, float* dW, float* db,
-                                       float* dX, int R, int C, void* stream) {
+static int classifier_backward(const float* x, long ldx, const float* W, const long long* labels, const float* saved,
+                               const float* dloss, const float* dlogits, float* scratch, float* dW, float* db, float* dX, int R,
+                               int C, int D, hipStream_t st) {
     SupLayout ly;
-    const int rc = sup_layout(R, 1, C, 0, &ly);
+    const int rc = sup_layout(R, 1, C, D, 0, &ly);
     if (rc) return rc;
-    CPC_RETURN_IF(!x || ldx < kC || !W || !scratch || !dW || !db, CPC_ERR_ARG);
+    CPC_RETURN_IF(!x || ldx < D || !W || !scratch || !dW || !db, CPC_ERR_ARG);
     CPC_RETURN_IF(!dlogits && (!labels || !saved || !dloss), CPC_ERR_ARG);
-    const hipStream_t st = (hipStream_t)stream;
     const float* dl = dlogits;
     if (!dl) {
         hipLaunchKernelGGL(sup_dlogits_kernel, dim3((R + 3) / 4), dim3(256), 0, st, saved + ly.logits, saved + ly.lse, labels,
@@ -344,39 +342,38 @@ extern "C" int cpc_classifier_backward(const float* x, long ldx, const float* W,
         CPC_LAUNCH_CHECK();
         dl = scratch + ly.dl;
     }
-    SupProd p{};                                   // partial dW of each row slab: (C x 256) = dl^T x
+    SupProd p{};                                   // partial dW of each row slab: (C x D) = dl^T x
     p.A = dl; p.sam = 1; p.sak = C;
     p.B = x; p.sbn = 1; p.sbk = ldx;
-    p.out = scratch + ly.part; p.ldc = kC; p.slab = (long)C * kC;
-    p.M = C; p.N = kC; p.K = R; p.kchunk = ly.kchunk;
+    p.out = scratch + ly.part; p.ldc = D; p.slab = (long)C * D;
+    p.M = C; p.N = D; p.K = R; p.kchunk = ly.kchunk;
     int r2 = sup_prod(p, ly.Z, st);
     if (r2) return r2;
     r2 = head_colsum(dl, scratch + ly.dbp, R, C, ly.kchunk, ly.Z, st);
     if (r2) return r2;
-    const long n = (long)C * kC + C;
+    const long n = (long)C * D + C;
     hipLaunchKernelGGL(sup_slab_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, scratch + ly.part,
-                       scratch + ly.dbp, dW, db, C, ly.Z);
+                       scratch + ly.dbp, dW, db, C, D, ly.Z);
     CPC_LAUNCH_CHECK();
-    if (dX) {                                      // dX (R x 256) = dl W
+    if (dX) {                                      // dX (R x D) = dl W
         SupProd q{};
         q.A = dl; q.sam = C; q.sak = 1;
-        q.B = W; q.sbn = 1; q.sbk = kC;
-        q.out = dX; q.ldc = kC; q.slab = 0;
-        q.M = R; q.N = kC; q.K = C; q.kchunk = C;
+        q.B = W; q.sbn = 1; q.sbk = D;
+        q.out = dX; q.ldc = D; q.slab = 0;
+        q.M = R; q.N = D; q.K = C; q.kchunk = C;
         r2 = sup_prod(q, 1, st);
         if (r2) return r2;
     }
     return 0;
 }
 
-extern "C" int cpc_ctc_forward(const float* x, const float* W, const float* b, const long long* labels, float* saved,
-                               float* loss, int B, int S, int C, void* stream) {
+static int ctc_forward(const float* x, const float* W, const float* b, const long long* labels, float* saved, float* loss, int B,
+                       int S, int C, int D, hipStream_t st) {
     SupLayout ly;
-    const int rc = sup_layout(B, S, C, 1, &ly);
+    const int rc = sup_layout(B, S, C, D, 1, &ly);
     if (rc) return rc;
     CPC_RETURN_IF(!x || !W || !b || !labels || !saved || !loss, CPC_ERR_ARG);
-    const hipStream_t st = (hipStream_t)stream;
-    const int r2 = sup_logits(x, kC, W, b, saved, ly, B * S, C, st);
+    const int r2 = sup_logits(x, D, W, b, saved, ly, B * S, C, D, st);
     if (r2) return r2;
     long long* targets = reinterpret_cast<long long*>(saved + ly.targets);
     long long* tgt_len = reinterpret_cast<long long*>(saved + ly.tgt_len);
@@ -386,9 +383,52 @@ extern "C" int cpc_ctc_forward(const float* x, const float* W, const float* b, c
     return ctc_loss_forward(saved + ly.logits, in_len, targets, S, tgt_len, saved + ly.ctc, loss, B, S, C, S, C - 1, kCtcMean, st);
 }
 
+}  // namespace cpc
+
+using namespace cpc;
+
+extern "C" int cpc_supervised_layout(int B, int S, int C, int ctc, long* sizes) { return sup_layout_sizes(B, S, C, kC, ctc, sizes); }
+
+extern "C" int cpc_supervised_layout_d(int B, int S, int C, int D, int ctc, long* sizes) {
+    return sup_layout_sizes(B, S, C, D, ctc, sizes);
+}
+
+extern "C" int cpc_classifier_forward(const float* x, long ldx, const float* W, const float* b, const long long* labels,
+                                      float* saved, float* loss, double* acc, int R, int C, void* stream) {
+    return classifier_forward(x, ldx, W, b, labels, saved, loss, acc, R, C, kC, (hipStream_t)stream);
+}
+
+extern "C" int cpc_classifier_forward_d(const float* x, long ldx, const float* W, const float* b, const long long* labels,
+                                        float* saved, float* loss, double* acc, int R, int C, int D, void* stream) {
+    return classifier_forward(x, ldx, W, b, labels, saved, loss, acc, R, C, D, (hipStream_t)stream);
+}
+
+extern "C" int cpc_classifier_backward(const float* x, long ldx, const float* W, const long long* labels, const float* saved,
+                                       const float* dloss, const float* dlogits, float* scratch, float* dW, float* db,
+                                       float* dX, int R, int C, void* stream) {
+    return classifier_backward(x, ldx, W, labels, saved, dloss, dlogits, scratch, dW, db, dX, R, C, kC, (hipStream_t)stream);
+}
+
+extern "C" int cpc_classifier_backward_d(const float* x, long ldx, const float* W, const long long* labels, const float* saved,
+                                         const float* dloss, const float* dlogits, float* scratch, float* dW, float* db,
+                                         float* dX, int R, int C, int D, void* stream) {
+    return classifier_backward(x, ldx, W, labels, saved, dloss, dlogits, scratch, dW, db, dX, R, C, D, (hipStream_t)stream);
+}
+
+extern "C" int cpc_ctc_forward(const float* x, const float* W, const float* b, const long long* labels, float* saved,
+                               float* loss, int B, int S, int C, void* stream) {
+    return ctc_forward(x, W, b, labels, saved, loss, B, S, C, kC, (hipStream_t)stream);
+}
+
+extern "C" int cpc_ctc_forward_d(const float* x, const float* W, const float* b, const long long* labels, float* saved,
+                                 float* loss, int B, int S, int C, int D, void* stream) {
+    return ctc_forward(x, W, b, labels, saved, loss, B, S, C, D, (hipStream_t)stream);
+}
+
+// (what it reads of ``saved`` -- the logits and the CTC loss's own block -- lies where it does at every feature width: no _d twin)
 extern "C" int cpc_ctc_backward(const float* saved, const float* dloss, float* dlogits, int B, int S, int C, void* stream) {
     SupLayout ly;
-    const int rc = sup_layout(B, S, C, 1, &ly);
+    const int rc = sup_layout(B, S, C, kC, 1, &ly);
     if (rc) return rc;
     CPC_RETURN_IF(!saved || !dloss || !dlogits, CPC_ERR_ARG);
     return ctc_loss_backward(saved + ly.logits, saved + ly.ctc, dloss, dlogits, B, S, C, S, C - 1, kCtcMean, (hipStream_t)stream);

@@ -10,9 +10,10 @@ checkpoint: ``--nGPU n`` only scales the batch to ``batchSizeGPU * n`` (the refe
 
 In the default frozen mode the step behind the feature forward -- classifier, cross-entropy, accuracy, both gradients and the
 Adam update -- is ONE C call (``ops.probe_train_step``, csrc/probe.hip) when ``FUSED_PROBE`` is set, the criterion is a
-SpeakerCriterion or PhoneCriterion on the HIP path (256 features, one layer) and the features are CUDA fp32.  Everything else
-(``--CTC``, ``--unfrozen``, other widths, the flag off) runs the criterion's autograd Function and ``optim.Adam.step()`` in the
-same loop; both write the same files.
+SpeakerCriterion or PhoneCriterion on the HIP path (one layer; 256 features, or with ``--wideKernel`` any width from 1 to 512:
+an MFCC, filter-bank, ``no_ar`` or ``hiddenGar 512`` checkpoint) and the features are CUDA fp32.  Everything else (``--CTC``,
+``--unfrozen``, the flag off) runs the criterion's autograd Function and ``optim.Adam.step()`` in the same loop -- on the library's
+kernels at 256 features and, with ``--wideKernel``, at the other widths, on torch ops otherwise; all write the same files.
 
 Two deliberate differences from the reference:
 
@@ -48,7 +49,9 @@ def get_module(module):
 def _probe_of(feature_maker, criterion):
     """The (classifier layer, kind) the fused probe step applies to, or None."""
     crit = get_module(criterion)
-    if not FUSED_PROBE or getattr(feature_maker, "optimize", True) or not getattr(crit, "hip_path", False):
+    if not FUSED_PROBE or getattr(feature_maker, "optimize", True):
+        return None
+    if not (getattr(crit, "hip_path", False) or getattr(crit, "hip_wide", False)):
         return None
     if isinstance(crit, cr.SpeakerCriterion):
         return crit.linearSpeakerClassifier, "speaker"
@@ -58,7 +61,7 @@ def _probe_of(feature_maker, criterion):
 
 
 def _probe_rows(criterion, kind, c_feature, encoded_data, label):
-    """What the criterion's forward would classify: (rows (R, 256), labels (R,)), or None when the features are not CUDA fp32."""
+    """What the criterion's forward would classify: (rows (R, D), labels (R,)), or None when the features are not CUDA fp32."""
     if kind == "speaker":
         features = c_feature[:, -1, :]                   # read in place through its row stride
     else:
@@ -229,6 +232,10 @@ def parse_args(argv):
     parser.add_argument('--epsilon', type=float, default=2e-8, help='Value of epsilon for the Adam optimizer.')
     parser.add_argument('--ignore_cache', action='store_true', help="Activate if the sequences in pathDB have changed.")
     parser.add_argument('--size_window', type=int, default=20480, help="Number of frames to consider in each batch.")
+    # (an addition.  Off by default, and then absent from the namespace: the reference's argument lists keep parsing to the
+    # reference's namespace, which is also what checkpoint_args.json records)
+    parser.add_argument('--wideKernel', action='store_true', default=argparse.SUPPRESS,
+                        help="Run the classifier on the HIP kernels at feature widths other than 256 as well (1 to 512).")
     args = parser.parse_args(argv)
     if args.nGPU < 0:
         args.nGPU = 1
@@ -243,6 +250,7 @@ def main(argv):
     from . import optim
     from .common_voices_eval import load_feature_maker
     args = parse_args(argv)
+    wide = getattr(args, "wideKernel", False)
     logs = {"epoch": [], "iter": [], "saveStep": args.save_step}
     if len(args.load) > 1:
         raise ValueError("concatenated models (more than one checkpoint) are not supported")
@@ -259,13 +267,13 @@ def main(argv):
         phone_labels, n_phones = parseSeqLabels(args.pathPhone)
         if not args.CTC:
             print("Running phone separability with aligned phones")
-            criterion = cr.PhoneCriterion(dim_features, n_phones, args.get_encoded)
+            criterion = cr.PhoneCriterion(dim_features, n_phones, args.get_encoded, wideKernel=wide)
         else:
             print("Running phone separability with CTC loss")
-            criterion = cr.CTCPhoneCriterion(dim_features, n_phones, args.get_encoded)
+            criterion = cr.CTCPhoneCriterion(dim_features, n_phones, args.get_encoded, wideKernel=wide)
     else:
         print("Running speaker separability")
-        criterion = cr.SpeakerCriterion(dim_features, len(speakers))
+        criterion = cr.SpeakerCriterion(dim_features, len(speakers), wideKernel=wide)
     criterion.cuda()
 
     seq_train = filterSeqs(args.pathTrain, seqNames)

@@ -776,39 +776,73 @@ def _rows_of(x, what):
     return x, max(int(x.stride(0)), _HID)
 
 
+CLASSIFIER_MAX_DIM = 512      # widest feature row of the _d entry points (cpc_probe_*_d, cpc_classifier_*_d, cpc_ctc_forward_d)
+
+
+def _rows_of_width(x, weight, what):
+    """(R, D) features with unit column stride for a (C, D) weight, 1 <= D <= CLASSIFIER_MAX_DIM: (x, row stride, D).  256 goes
+    through _rows_of and on to the 256 entry points, any other D to the _d ones."""
+    if weight.dim() != 2:
+        raise ValueError(f"{what}: a (C, D) weight expected, got {tuple(weight.shape)}")
+    D = weight.shape[1]
+    if x.dim() != 2 or x.shape[1] != D:
+        raise ValueError(f"{what}: features of shape {tuple(x.shape)} for a weight of shape {tuple(weight.shape)}")
+    _require_cuda(x, what)
+    if D == _HID:
+        return (*_rows_of(x, what), D)
+    if not 1 <= D <= CLASSIFIER_MAX_DIM:
+        raise NotImplementedError(f"cpc_audio_amd.{what}: the HIP classifier takes 1 to {CLASSIFIER_MAX_DIM} input features, got {D}")
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < D):
+        x = x.contiguous()
+    return x, max(int(x.stride(0)), D), D
+
+
+def _supervised_layout(lib, B, S, C, D, ctc):
+    if D == _HID:
+        return _layout("supervised_layout", lib.cpc_supervised_layout, 3, B, S, C, ctc)
+    return _layout("supervised_layout_d", lib.cpc_supervised_layout_d, 3, B, S, C, D, ctc)
+
+
 def _classifier_backward(x, ldx, weight, label, saved, dloss, dlogits, R, C, need_dx):
     lib = _lib.get()
-    sizes = _layout("supervised_layout", lib.cpc_supervised_layout, 3, R, 1, C, 0)
+    D = weight.shape[1]
+    sizes = _supervised_layout(lib, R, 1, C, D, 0)
     scratch = torch.empty(sizes[1], device=x.device, dtype=torch.float32)
     dW, db = torch.empty_like(weight), torch.empty(C, device=x.device, dtype=torch.float32)
-    dx = torch.empty(R, _HID, device=x.device, dtype=torch.float32) if need_dx else None
-    lib.check(lib.cpc_classifier_backward(x.data_ptr(), ldx, _p(weight), _p(label), _p(saved), _p(dloss), _p(dlogits),
-                                          _p(scratch), _p(dW), _p(db), _p(dx), R, C, _stream()), "classifier_backward")
+    dx = torch.empty(R, D, device=x.device, dtype=torch.float32) if need_dx else None
+    args = (x.data_ptr(), ldx, _p(weight), _p(label), _p(saved), _p(dloss), _p(dlogits), _p(scratch), _p(dW), _p(db), _p(dx), R, C)
+    if D == _HID:
+        lib.check(lib.cpc_classifier_backward(*args, _stream()), "classifier_backward")
+    else:
+        lib.check(lib.cpc_classifier_backward_d(*args, D, _stream()), "classifier_backward_d")
     return dx, dW, db
 
 
 class ClassifierXentFunction(torch.autograd.Function):
-    """x (R,256) (any row stride), label (R,) int64, weight (C,256), bias (C,) -> loss (1,1) float32, acc (1,1) float64:
+    """x (R,D) (any row stride), label (R,) int64, weight (C,D), bias (C,) -> loss (1,1) float32, acc (1,1) float64:
     nn.Linear + nn.CrossEntropyLoss() and (argmax == label).double().mean() (cpc/criterion/criterion.py:198-203, 226-231).
+    D = 256 runs cpc_classifier_forward / _backward, any other D from 1 to 512 their _d twins.
     acc is not differentiable; x receives a gradient only when it requires one."""
 
     @staticmethod
     def forward(ctx, x, label, weight, bias):
-        _require_cuda(x, "ClassifierXentFunction")
+        x, ldx, D = _rows_of_width(x, weight, "ClassifierXentFunction")     # (a CPU tensor raises there)
         lib = _lib.get()
-        x, ldx = _rows_of(x, "ClassifierXentFunction")
         R, C = x.shape[0], weight.shape[0]
         label = _labels_on(label, x.device).view(-1)
         if label.numel() != R:
             raise ValueError(f"ClassifierXentFunction: {label.numel()} labels for {R} feature rows")
         weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
         with torch.cuda.device(x.device):
-            sizes = _layout("supervised_layout", lib.cpc_supervised_layout, 3, R, 1, C, 0)
+            sizes = _supervised_layout(lib, R, 1, C, D, 0)
             saved = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
             loss = torch.empty(1, 1, device=x.device, dtype=torch.float32)
             acc = torch.empty(1, 1, device=x.device, dtype=torch.float64)
-            lib.check(lib.cpc_classifier_forward(x.data_ptr(), ldx, _p(weight), _p(bias), _p(label), _p(saved), _p(loss),
-                                                 _p(acc), R, C, _stream()), "classifier_forward")
+            args = (x.data_ptr(), ldx, _p(weight), _p(bias), _p(label), _p(saved), _p(loss), _p(acc), R, C)
+            if D == _HID:
+                lib.check(lib.cpc_classifier_forward(*args, _stream()), "classifier_forward")
+            else:
+                lib.check(lib.cpc_classifier_forward_d(*args, D, _stream()), "classifier_forward_d")
         ctx.save_for_backward(x, label, weight, saved)
         ctx.dims = (ldx, R, C)
         ctx.mark_non_differentiable(acc)
@@ -827,17 +861,21 @@ class ClassifierXentFunction(torch.autograd.Function):
 
 
 class CtcXentFunction(torch.autograd.Function):
-    """x (B,S,256), label (B,S) int64 frame labels, weight (C,256), bias (C,) -> loss (1,1) float32: nn.Linear, log_softmax
+    """x (B,S,D), label (B,S) int64 frame labels, weight (C,D), bias (C,) -> loss (1,1) float32: nn.Linear, log_softmax
     and nn.CTCLoss(blank=C-1, zero_infinity=True) on the collapsed labels with every input length S
-    (cpc/criterion/criterion.py:265-283), 1 <= S <= CTC_MAX_SEQ."""
+    (cpc/criterion/criterion.py:265-283), 1 <= S <= CTC_MAX_SEQ.  D = 256 runs cpc_ctc_forward, any other D from 1 to 512
+    cpc_ctc_forward_d."""
 
     @staticmethod
     def forward(ctx, x, label, weight, bias):
+        if weight.dim() != 2 or x.dim() != 3 or x.shape[2] != weight.shape[1]:
+            raise ValueError(f"CtcXentFunction: features of shape {tuple(x.shape)} for a weight of shape {tuple(weight.shape)}")
         _require_cuda(x, "CtcXentFunction")
         lib = _lib.get()
-        if x.dim() != 3 or x.shape[2] != _HID:
-            raise NotImplementedError("cpc_audio_amd.CtcXentFunction: the HIP classifier is built for 256 input features")
-        B, S, _ = x.shape
+        B, S, D = x.shape
+        if not 1 <= D <= CLASSIFIER_MAX_DIM:
+            raise NotImplementedError(f"cpc_audio_amd.CtcXentFunction: the HIP classifier takes 1 to {CLASSIFIER_MAX_DIM} input "
+                                      f"features, got {D}")
         C = weight.shape[0]
         if S > CTC_MAX_SEQ:
             raise ValueError(f"CtcXentFunction: sequences of at most {CTC_MAX_SEQ} frames are supported (got {S})")
@@ -847,11 +885,14 @@ class CtcXentFunction(torch.autograd.Function):
         x = x.contiguous()
         weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
         with torch.cuda.device(x.device):
-            sizes = _layout("supervised_layout", lib.cpc_supervised_layout, 3, B, S, C, 1)
+            sizes = _supervised_layout(lib, B, S, C, D, 1)
             saved = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
             loss = torch.empty(1, 1, device=x.device, dtype=torch.float32)
-            lib.check(lib.cpc_ctc_forward(_p(x), _p(weight), _p(bias), _p(label), _p(saved), _p(loss), B, S, C, _stream()),
-                      "ctc_forward")
+            args = (_p(x), _p(weight), _p(bias), _p(label), _p(saved), _p(loss), B, S, C)
+            if D == _HID:
+                lib.check(lib.cpc_ctc_forward(*args, _stream()), "ctc_forward")
+            else:
+                lib.check(lib.cpc_ctc_forward_d(*args, D, _stream()), "ctc_forward_d")
         ctx.save_for_backward(x, weight, saved)
         ctx.dims = (B, S, C, sizes[2])
         return loss
@@ -866,8 +907,9 @@ class CtcXentFunction(torch.autograd.Function):
         with torch.cuda.device(x.device):
             dlogits = torch.empty(ndl, device=x.device, dtype=torch.float32)
             lib.check(lib.cpc_ctc_backward(_p(saved), _p(dloss.contiguous()), _p(dlogits), B, S, C, _stream()), "ctc_backward")
-            dx, dW, db = _classifier_backward(x, _HID, weight, None, None, None, dlogits, B * S, C, ctx.needs_input_grad[0])
-        return (None if dx is None else dx.view(B, S, _HID)), None, dW, db
+            D = weight.shape[1]
+            dx, dW, db = _classifier_backward(x, D, weight, None, None, None, dlogits, B * S, C, ctx.needs_input_grad[0])
+        return (None if dx is None else dx.view(B, S, D)), None, dW, db
 
 
 # ---- the PER phone classifier (csrc/phone_head.hip) ----------------------------------------------------------------------
@@ -1272,20 +1314,22 @@ _probe_workspaces = {}
 
 
 def _probe_setup(x, label, weight, what):
-    _require_cuda(x, what)
-    x, ldx = _rows_of(x, what)
+    x, ldx, D = _rows_of_width(x, weight, what)                              # (a CPU tensor raises there)
     R, C = x.shape[0], weight.shape[0]
     label = _labels_on(label, x.device).view(-1)
     if label.numel() != R:
         raise ValueError(f"{what}: {label.numel()} labels for {R} feature rows")
     lib = _lib.get()
     stream = _stream()
-    key = (R, C, x.device, stream)
+    key = (R, C, D, x.device, stream)
     ws = _probe_workspaces.get(key)
     if ws is None:                                       # once per shape (and stream: calls on one stream are ordered)
-        sizes = _layout("probe_layout", lib.cpc_probe_layout, 3, R, C)
+        if D == _HID:
+            sizes = _layout("probe_layout", lib.cpc_probe_layout, 3, R, C)
+        else:
+            sizes = _layout("probe_layout_d", lib.cpc_probe_layout_d, 3, R, C, D)
         ws = _probe_workspaces[key] = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
-    return lib, x, ldx, label, R, C, ws, stream
+    return lib, x, ldx, label, R, C, D, ws, stream
 
 
 def _probe_outputs(x, out):
@@ -1296,11 +1340,12 @@ def _probe_outputs(x, out):
 
 @torch.no_grad()
 def probe_train_step(x, label, weight, bias, optimizer, accum=None, out=None, grads=None):
-    """One frozen probe step (cpc_probe_train_step): x (R,256) (any row stride), label (R,) -> loss (1,1) float32 and acc (1,1)
+    """One frozen probe step (cpc_probe_train_step; weight (C,D) with D != 256: cpc_probe_train_step_d): x (R,D) (any row
+    stride), label (R,) -> loss (1,1) float32 and acc (1,1)
     float64 of nn.Linear(weight, bias) + mean cross-entropy BEFORE the update, and ``optimizer`` (optim.Adam)'s update of
     weight and bias in place, moments and step count included.  accum: two device doubles that receive += loss, += acc;
     out: (loss, acc) tensors to write instead of new ones; grads: (dW, db) tensors that receive the gradients."""
-    lib, x, ldx, label, R, C, ws, stream = _probe_setup(x, label, weight, "probe_train_step")
+    lib, x, ldx, label, R, C, D, ws, stream = _probe_setup(x, label, weight, "probe_train_step")
     for p in (weight, bias):
         if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
             raise TypeError("probe_train_step: dense fp32 parameters on the GPU expected")
@@ -1310,21 +1355,27 @@ def probe_train_step(x, label, weight, bias, optimizer, accum=None, out=None, gr
     dW, db = grads if grads is not None else (None, None)
     beta1, beta2 = group["betas"]
     with torch.cuda.device(x.device):
-        lib.check(lib.cpc_probe_train_step(x.data_ptr(), ldx, _p(label), R, C, _p(weight), _p(bias), _p(mW), _p(vW), _p(mb),
-                                           _p(vb), float(group["lr"]), beta1, beta2, float(group["eps"]), bc1, bc2s, _p(ws),
-                                           _p(loss), _p(acc), _p(accum), _p(dW), _p(db), stream), "probe_train_step")
+        tail = (_p(weight), _p(bias), _p(mW), _p(vW), _p(mb), _p(vb), float(group["lr"]), beta1, beta2, float(group["eps"]), bc1,
+                bc2s, _p(ws), _p(loss), _p(acc), _p(accum), _p(dW), _p(db), stream)
+        if D == _HID:
+            lib.check(lib.cpc_probe_train_step(x.data_ptr(), ldx, _p(label), R, C, *tail), "probe_train_step")
+        else:
+            lib.check(lib.cpc_probe_train_step_d(x.data_ptr(), ldx, _p(label), R, C, D, *tail), "probe_train_step_d")
     return loss, acc
 
 
 @torch.no_grad()
 def probe_eval(x, label, weight, bias, accum=None, out=None):
-    """Loss (1,1) float32 and accuracy (1,1) float64 of the linear classifier on x (R,256), label (R,) (cpc_probe_eval);
-    accum / out as in probe_train_step."""
-    lib, x, ldx, label, R, C, ws, stream = _probe_setup(x, label, weight, "probe_eval")
+    """Loss (1,1) float32 and accuracy (1,1) float64 of the linear classifier on x (R,D), label (R,) (cpc_probe_eval; D != 256:
+    cpc_probe_eval_d); accum / out as in probe_train_step."""
+    lib, x, ldx, label, R, C, D, ws, stream = _probe_setup(x, label, weight, "probe_eval")
     loss, acc = _probe_outputs(x, out)
     with torch.cuda.device(x.device):
-        lib.check(lib.cpc_probe_eval(x.data_ptr(), ldx, _p(label), R, C, _p(weight.detach().contiguous()),
-                                     _p(bias.detach().contiguous()), _p(ws), _p(loss), _p(acc), _p(accum), stream), "probe_eval")
+        tail = (_p(weight.detach().contiguous()), _p(bias.detach().contiguous()), _p(ws), _p(loss), _p(acc), _p(accum), stream)
+        if D == _HID:
+            lib.check(lib.cpc_probe_eval(x.data_ptr(), ldx, _p(label), R, C, *tail), "probe_eval")
+        else:
+            lib.check(lib.cpc_probe_eval_d(x.data_ptr(), ldx, _p(label), R, C, D, *tail), "probe_eval_d")
     return loss, acc
 
 

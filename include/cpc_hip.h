@@ -449,6 +449,18 @@ int cpc_classifier_backward(const float* x, long ldx, const float* W, const long
 int cpc_ctc_forward(const float* x, const float* W, const float* b, const long long* labels, float* saved, float* loss, int B,
                     int S, int C, void* stream);
 int cpc_ctc_backward(const float* saved, const float* dloss, float* dlogits, int B, int S, int C, void* stream);
+/* The same criteria on D features per row, 1 <= D <= 512 (CPC_ERR_SHAPE beyond; checked first): x rows of D floats at
+ * x + r * ldx (ldx >= D, else CPC_ERR_ARG; the CTC call: dense), W (C,D), dW (C,D) and dX (R,D) dense at pitch D; everything else
+ * as above.  The same host code and kernels as the 256 entry points, which pass 256: D = 256 gives their bits.
+ * cpc_ctc_backward serves every width: the logits and the loss's block lie in ``saved`` where they do at 256. */
+int cpc_supervised_layout_d(int B, int S, int C, int D, int ctc, long* sizes);
+int cpc_classifier_forward_d(const float* x, long ldx, const float* W, const float* b, const long long* labels, float* saved,
+                             float* loss, double* acc, int R, int C, int D, void* stream);
+int cpc_classifier_backward_d(const float* x, long ldx, const float* W, const long long* labels, const float* saved,
+                              const float* dloss, const float* dlogits, float* scratch, float* dW, float* db, float* dX, int R,
+                              int C, int D, void* stream);
+int cpc_ctc_forward_d(const float* x, const float* W, const float* b, const long long* labels, float* saved, float* loss, int B,
+                      int S, int C, int D, void* stream);
 
 /* ------------------------------------------------------- PER phone classifier ----
  * CTCphone_criterion of cpc/eval/common_voices_eval.py: nn.Conv1d(256, C, 8, stride 4) on the features, log_softmax and
@@ -608,6 +620,20 @@ int cpc_probe_train_step(const float* x, long ldx, const long long* labels, int 
                          double* acc, double* accum, float* dW_out, float* db_out, void* stream);
 int cpc_probe_eval(const float* x, long ldx, const long long* labels, int R, int C, const float* W, const float* b,
                    float* workspace, float* loss, double* acc, double* accum, void* stream);
+/* The same step on D features per row, 1 <= D <= 512 (CPC_ERR_SHAPE beyond; checked first): row r of x at x + r * ldx with
+ * ldx >= D (else CPC_ERR_ARG) read in place, W (C,D) dense, the moments, dW_out and the workspace's partials dense at pitch D;
+ * the workspace is sized by cpc_probe_layout_d and nothing else.  Every logit is the fmaf chain over k = 0 .. D - 1 in that
+ * order, in both walks; LDS rows are padded with zeros to the next multiple of 4 only, and the k loop follows D.  x and W are
+ * read 16 bytes at a time where base, row pitch and D allow (base 16-byte aligned, ldx % 4 == 0, D % 4 == 0), one float at a
+ * time otherwise.  64 classes per step up to 256 features, 32 above (csrc/probe.hip: probe_wide_kernel).  D = 256 gives the bits
+ * of the calls above; limits, flags, orders and everything else are theirs. */
+int cpc_probe_layout_d(int R, int C, int D, long* sizes);
+int cpc_probe_train_step_d(const float* x, long ldx, const long long* labels, int R, int C, int D, float* W, float* b,
+                           float* exp_avg_W, float* exp_avg_sq_W, float* exp_avg_b, float* exp_avg_sq_b, double lr, double beta1,
+                           double beta2, double eps, double bias_correction1, double bias_correction2_sqrt, float* workspace,
+                           float* loss, double* acc, double* accum, float* dW_out, float* db_out, void* stream);
+int cpc_probe_eval_d(const float* x, long ldx, const long long* labels, int R, int C, int D, const float* W, const float* b,
+                     float* workspace, float* loss, double* acc, double* accum, void* stream);
 
 /* ------------------------------------------------------------ phone posteriors ----
  * What cpc/feature_loader.py:61-71 (ModelPhoneCombined.forward) computes behind the feature maker: the linear classifier of
