@@ -120,6 +120,9 @@ SIGNATURES = {
     "cpc_gru_backward_coef": (_I, [_P] * 5 + [_I, _I, _I, _I, _P]),
     "cpc_gru_backward_with_coef": (_I, [_P] * 10 + [_I, _I, _I, _P]),
     "cpc_gru_backward_streams": (_I, [_P] * 10 + [_I, _I, _I, _P, _P]),
+    "cpc_gru_forward_prepare_steps": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "cpc_gru_forward_coef_prepared_steps": (_I, [_P] * 8 + [_I, _I, _I, _I, _P]),
+    "cpc_gru_backward_streams_steps": (_I, [_P] * 10 + [_I, _I, _I, _I, _P, _P]),
     "cpc_lstm_layout": (_I, [_I, _I, _I, _P]),
     "cpc_lstm_forward": (_I, [_P] * 9 + [_I, _I, _I, _I, _P]),
     "cpc_lstm_backward": (_I, [_P] * 10 + [_I, _I, _I, _I, _P]),

@@ -190,6 +190,8 @@ struct Gru2Fwd {
                                // frag_stride floats apart, fragment order) -- written by the gate threads, which hold every input
     long frag_stride;          // of gru_bwd_coef_kernel in registers: that kernel's 75 MB read-back is not needed then
     int B, S;
+    int T;                     // active steps, 1 <= T <= S: steps t >= T are not run (and hN is not written unless T == S); S stays the
+                               // stride of every address.  All wave kinds of a launch bound their time loops by this one number
     int spin_limit;            // persistent launch only: polling budget of a wave (cpc_set_gru_spin_limit)
     int ntiles, xcd_pack;      // persistent launch only: see PersistIds
     int tile0, total_tiles;    // persistent launch only: this launch covers batch tiles [tile0, tile0 + ntiles) of total_tiles
@@ -241,7 +243,7 @@ __global__ __launch_bounds__(512) void gru2_fwd_kernel(Gru2Fwd p, int s) {
     __shared__ float part[8][3][256];
     const int layer = blockIdx.z;
     const int t = layer == 0 ? s : s - 1;
-    if (t < 0 || t >= p.S) return;                         // block-uniform
+    if (t < 0 || t >= p.T) return;                         // block-uniform
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int i = lane & 15, kq = lane >> 4;
     const int j0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
@@ -330,6 +332,8 @@ struct Gru2Bwd {
     float* xdh1r;              // persistent launch with the (tile, layer) group numbering only, else NULL: a second copy of xdh[1],
                                // always stored device scope, for layer 0's look across the XCDs (persist_bwd)
     int B, S;
+    int T;                     // active steps, 1 <= T <= S: the caller promises dy[:, T:] == 0, the recurrence starts at t = T - 1 with an
+                               // incoming dh of zero (what the full run has there) and rows t >= T of dGi / dGh / DH are written as zeros
     int spin_limit;            // persistent launch only: polling budget of a wave (cpc_set_gru_spin_limit)
     int ntiles, xcd_pack;      // persistent launch only: see PersistIds
     int tile0, total_tiles;    // persistent launch only: this launch covers batch tiles [tile0, tile0 + ntiles) of total_tiles
@@ -418,18 +422,18 @@ __device__ __forceinline__ f32x4 mfma_gate_rows(f32x4 acc, const float* __restri
     return add4(acc, add4(add4(ag[0], ag[1]), ag[2]));
 }
 
-// Launch s (s = 0..S): blockIdx.z = 0 -> top layer (1) step t = S-1-s; blockIdx.z = 1 -> bottom
-// layer (0) step t = S-s, whose incoming gradient dGi1_t . W_ih1 is formed on the fly (waves 4-7).
+// Launch s (s = 0..T, T = p.T active steps): blockIdx.z = 0 -> top layer (1) step t = T-1-s; blockIdx.z = 1 -> bottom
+// layer (0) step t = T-s, whose incoming gradient dGi1_t . W_ih1 is formed on the fly (waves 4-7).
 __global__ __launch_bounds__(512) void gru2_bwd_kernel(Gru2Bwd p, int s) {
     __shared__ float part[8][256];
     const int layer = blockIdx.z == 0 ? 1 : 0;
-    const int S = p.S, B = p.B;
-    const int t = layer == 1 ? S - 1 - s : S - s;
-    if (t < 0 || t >= S) return;                           // block-uniform
+    const int S = p.S, B = p.B, T = p.T;
+    const int t = layer == 1 ? T - 1 - s : T - s;
+    if (t < 0 || t >= T) return;                           // block-uniform
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int i = lane & 15, kq = lane >> 4;
     const int j0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
-    const bool has_next = (t + 1) < S;
+    const bool has_next = (t + 1) < T;
 
     const int row = (tid & 255) >> 4, col = tid & 15;
     const int b = b0 + row, j = j0 + col;
@@ -692,7 +696,7 @@ __device__ __forceinline__ void persist_fwd(const Gru2Fwd& p, float (&part)[2][8
     const int j0 = id.j0;
     constexpr int NII = LAYER == 0 ? 2 : 4;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int B = p.B, S = p.S;
+    const int B = p.B, S = p.S, T = p.T;
     float* __restrict__ yl = p.y[LAYER];
     int tl[NT];                                      // this workgroup's batch tiles (tl[k] >= ntiles: none)
 #pragma unroll
@@ -721,7 +725,7 @@ __device__ __forceinline__ void persist_fwd(const Gru2Fwd& p, float (&part)[2][8
         PollPace pace(p.first_sleep);
         PhaseClock pc;
         pc.start();
-        for (int t = 0; t < S; ++t) {
+        for (int t = 0; t < T; ++t) {
             const bool traced = t >= 16 && t < S - 16;
 #pragma unroll
             for (int k = 0; k < NT; ++k) {
@@ -791,7 +795,7 @@ __device__ __forceinline__ void persist_fwd(const Gru2Fwd& p, float (&part)[2][8
     const int cpos = xpos(e >> 4, j);
     PhaseClock pc;
     pc.start();
-    for (int t = 0; t < S; ++t) {
+    for (int t = 0; t < T; ++t) {
         const bool traced = t >= 16 && t < S - 16;
 #pragma unroll
         for (int k = 0; k < NT; ++k) {
@@ -841,7 +845,7 @@ __device__ __forceinline__ void persist_fwd(const Gru2Fwd& p, float (&part)[2][8
                 cf[c + 3 * p.frag_stride] = a;                        // cni
             }
             hp[k] = h;
-            if (LAYER == 0 && t + 1 < S) {                            // next step's input projection, a step ahead
+            if (LAYER == 0 && t + 1 < T) {                            // next step's input projection, a step ahead
                 const float* gip = p.x_gi0 + (bt + 1) * kG;
                 gi[k][0] = gip[j]; gi[k][1] = gip[kH + j]; gi[k][2] = gip[2 * kH + j];
             }
@@ -904,7 +908,7 @@ __device__ __forceinline__ void persist_bwd(const Gru2Bwd& p, float (&part)[2][8
     constexpr int NU = LAYER == 1 ? 2 : 4;           // unit fragments per lane (x 3 gates = MFMA fragments)
     const int j0 = id.j0;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int B = p.B, S = p.S;
+    const int B = p.B, S = p.S, T = p.T;         // (T bounds the time loops of EVERY wave kind below; S only addresses)
     int tl[NT];
 #pragma unroll
     for (int k = 0; k < NT; ++k) tl[k] = id.tile + k * id.G;
@@ -936,18 +940,18 @@ __device__ __forceinline__ void persist_bwd(const Gru2Bwd& p, float (&part)[2][8
             bok[k] = tok[k] && (tl[k] * 16 + i) < B;
         }
         float4 cf[NU][3];
-        if (NT == 1 && !recurrent) load_coef<NU>(cf, c0, c1, c2, xtile(S - 1, tl[0], id.ntiles, kH) + lane_off);
+        if (NT == 1 && !recurrent) load_coef<NU>(cf, c0, c1, c2, xtile(T - 1, tl[0], id.ntiles, kH) + lane_off);
         int budget = p.spin_limit;
         PollPace pace(p.first_sleep);
         PhaseClock pc;
         pc.start();
-        for (int t = S - 1; t >= 0; --t) {
+        for (int t = T - 1; t >= 0; --t) {
             const int ts = recurrent ? t + 1 : t;                 // step whose gate gradients are this wave's operand
             const bool traced = t >= 16 && t < S - 16;
 #pragma unroll
             for (int k = 0; k < NT; ++k) {
                 f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (ts < S && tok[k]) {
+                if (ts < T && tok[k]) {
                     if (NT > 1) load_coef<NU>(cf, c0, c1, c2, xtile(ts, tl[k], id.ntiles, kH) + lane_off);
                     float4 dh[NU];
                     poll_row<NU>(xsrc + xtile(ts, tl[k], id.ntiles, kH), bok[k], dh, budget, pace,
@@ -1018,11 +1022,30 @@ __device__ __forceinline__ void persist_bwd(const Gru2Bwd& p, float (&part)[2][8
         live[k] = tl[k] < id.ntiles && b[k] < B;
         dyv[k] = z[k] = cr[k] = cz[k] = cnh[k] = cni[k] = 0.f;
         dh_next[k] = z_next[k] = 0.f;
-        if (live[k]) fetch(k, S - 1);
+        if (live[k]) fetch(k, T - 1);
     }
+    // Steps t >= T carry no gradient: their rows of dGi / dGh / DH, which the dX and weight-gradient GEMMs read over all S steps, are
+    // the zeros the full run computes there (sums and products of zeros against finite coefficients).  No polling, no hand-over;
+    // layer 0 -- which starts a step behind layer 1 -- writes them on its way in, layer 1 -- done a step ahead -- on its way out.
+    auto zero_tail = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < NT; ++k) {
+            if (!live[k]) continue;
+            for (int t = T; t < S; ++t) {
+                const long bt = (long)b[k] * S + t;
+                float* gi = p.dGi[LAYER] + bt * kG;
+                float* gh = p.dGh[LAYER] + bt * kG;
+                __builtin_nontemporal_store(0.f, gi + j); __builtin_nontemporal_store(0.f, gh + j);
+                __builtin_nontemporal_store(0.f, gi + kH + j); __builtin_nontemporal_store(0.f, gh + kH + j);
+                __builtin_nontemporal_store(0.f, gi + 2 * kH + j); __builtin_nontemporal_store(0.f, gh + 2 * kH + j);
+                __builtin_nontemporal_store(0.f, p.DH[LAYER] + bt * kH + j);
+            }
+        }
+    };
+    if (LAYER == 0) zero_tail();
     PhaseClock pc;
     pc.start();
-    for (int t = S - 1; t >= 0; --t) {
+    for (int t = T - 1; t >= 0; --t) {
         const bool traced = t >= 16 && t < S - 16;
 #pragma unroll
         for (int k = 0; k < NT; ++k) {
@@ -1032,7 +1055,7 @@ __device__ __forceinline__ void persist_bwd(const Gru2Bwd& p, float (&part)[2][8
             const long bt = (long)b[k] * S + t;
             float (&pt)[8][256] = part[(t * NT + k) & 1];
             float dh0 = LAYER == 1 ? dyv[k] : 0.f;
-            if ((t + 1) < S) dh0 = fmaf(dh_next[k], z_next[k], dh0);
+            if ((t + 1) < T) dh0 = fmaf(dh_next[k], z_next[k], dh0);
             const float dh = (((pt[0][e] + pt[1][e]) + (pt[2][e] + pt[3][e])) +
                               ((pt[4][e] + pt[5][e]) + (pt[6][e] + pt[7][e]))) + dh0;
             store_handover(p.xdh[LAYER] + xtile(t, tl[k], id.ntiles, kH) + xp, dh, local);   // first: others wait for it
@@ -1055,6 +1078,7 @@ __device__ __forceinline__ void persist_bwd(const Gru2Bwd& p, float (&part)[2][8
             pc.lap(5, traced);
         }
     }
+    if (LAYER == 1) zero_tail();
     pc.flush(1);
 }
 
@@ -1069,6 +1093,16 @@ __global__ __launch_bounds__(kPersistThreads) void gru2_persist_bwd_kernel(Gru2B
     const bool local = p.xsync != nullptr && on_one_xcd(p.xsync + 4 * id.tile + (group ? 2 * id.layer : 0), p.spin_limit, group ? 16u : 32u);
     if (id.layer == 0) persist_bwd<1, NT>(p, part, id, local);    // the top layer leads
     else persist_bwd<0, NT>(p, part, id, local);
+}
+
+// Rows t >= T of a (B,S,4*w4) array zeroed: what a recurrence over T active steps leaves unwritten and later GEMMs read over all
+// S steps (0 * NaN is NaN, and the workspaces are not cleared).  grid = ceil(B*(S-T)*w4 / 256) blocks of 256 threads.
+__global__ __launch_bounds__(256) void gru_zero_tail_kernel(float* __restrict__ a, int B, int S, int T, int w4) {
+    const long per = (long)(S - T) * w4;                       // float4 per sequence
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)B * per) return;
+    const long b = i / per, r = i - b * per;
+    reinterpret_cast<float4*>(a + (b * S + T) * 4L * w4)[r] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 // ------------------------------------------------------------------ host side
@@ -1313,7 +1347,12 @@ extern "C" int cpc_gru_forward(const float* x, const float* h0, const float* con
 // -- by the persistent forward's gate threads where that path runs, by gru_bwd_coef_kernel behind the forward otherwise --
 // and cpc_gru_backward_coef(..., coef_done = 1) only has the hand-over buffers and the weight transposes left to prepare.
 static int gru_forward_impl(const float* x, const float* h0, const float* const* params, float* saved, float* scratch, float* y,
-                            float* hN, float* coef, int B, int S, int nl, void* stream, bool xh_ready, int D = kH);
+                            float* hN, float* coef, int B, int S, int nl, void* stream, bool xh_ready, int D = kH, int T = -1);
+static void launch_zero_tail(float* a, int B, int S, int T, int width, hipStream_t st) {
+    const long n = (long)B * (S - T) * (width / 4);
+    if (n > 0) hipLaunchKernelGGL(gru_zero_tail_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, a, B, S, T, width / 4);
+}
+
 extern "C" int cpc_gru_forward_coef(const float* x, const float* h0, const float* const* params, float* saved,
                                     float* scratch, float* y, float* hN, float* coef, int B, int S, int nl, void* stream) {
     return gru_forward_impl(x, h0, params, saved, scratch, y, hN, coef, B, S, nl, stream, false);
@@ -1332,6 +1371,29 @@ extern "C" int cpc_gru_forward_coef_prepared(const float* x, const float* h0, co
                                              float* scratch, float* y, float* hN, float* coef, int B, int S, int nl, void* stream) {
     return gru_forward_impl(x, h0, params, saved, scratch, y, hN, coef, B, S, nl, stream, true);
 }
+// The same pair for a forward over the first T steps only (1 <= T <= S; a caller that reads neither hN nor y beyond step T - 1).
+// The preparation also zeroes what the shortened recurrence leaves unwritten and the backward's GEMMs read over all S steps: rows
+// t >= T of y and of layer 0's output in `saved` (layer 1's input, and the "previous h" rows of both layers).  The gate values
+// saved for those steps stay unwritten: only cpc_gru_backward_streams_steps with the same T (or a smaller one) may follow.
+// hN is written only when T == S, where both calls are exactly the two above.
+extern "C" int cpc_gru_forward_prepare_steps(float* scratch, float* saved, float* y, int B, int S, int T, int nl, void* stream) {
+    GruLayout g;
+    CPC_RETURN_IF(nl != 2 || !gru_layout(B, S, nl, g), CPC_ERR_SHAPE);
+    CPC_RETURN_IF(!scratch || !saved || !y || T < 1 || T > S, CPC_ERR_ARG);
+    const int rc = cpc_gru_forward_prepare(scratch, B, S, nl, stream);
+    if (rc || T == S) return rc;
+    launch_zero_tail(y, B, S, T, kH, (hipStream_t)stream);
+    launch_zero_tail(saved + g.Y[0], B, S, T, kH, (hipStream_t)stream);
+    CPC_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int cpc_gru_forward_coef_prepared_steps(const float* x, const float* h0, const float* const* params, float* saved,
+                                                   float* scratch, float* y, float* hN, float* coef, int B, int S, int T, int nl,
+                                                   void* stream) {
+    CPC_RETURN_IF(nl != 2, CPC_ERR_SHAPE);
+    CPC_RETURN_IF(T < 1 || T > S, CPC_ERR_ARG);
+    return gru_forward_impl(x, h0, params, saved, scratch, y, hN, coef, B, S, nl, stream, true, kH, T);
+}
 // D: x is (B,S,D) and weight_ih_l0 (3H,D) (cpc_gru_forward_in); layer 0's input projection then runs in in_proj.hip
 extern "C" int cpc_gru_layout_in(int B, int S, int nl, int D, long* sizes) {
     GruLayout g;
@@ -1342,10 +1404,12 @@ extern "C" int cpc_gru_forward_in(const float* x, const float* h0, const float* 
     return gru_forward_impl(x, h0, params, saved, scratch, y, hN, nullptr, B, S, nl, stream, false, D);
 }
 static int gru_forward_impl(const float* x, const float* h0, const float* const* params, float* saved, float* scratch, float* y,
-                            float* hN, float* coef, int B, int S, int nl, void* stream, bool xh_ready, int D) {
+                            float* hN, float* coef, int B, int S, int nl, void* stream, bool xh_ready, int D, int T) {
     GruLayout g;
     CPC_RETURN_IF(!gru_layout(B, S, nl, g, D), CPC_ERR_SHAPE);
     CPC_RETURN_IF(!x || !params || !saved || !scratch || !y || !hN, CPC_ERR_ARG);
+    if (T < 0) T = S;                                // (every entry but the _steps ones)
+    CPC_RETURN_IF(T < 1 || T > S || (T != S && nl != 2), CPC_ERR_ARG);
     hipStream_t st = (hipStream_t)stream;
     const float* in = x;
     float* gi = scratch + g.gi;
@@ -1362,7 +1426,7 @@ static int gru_forward_impl(const float* x, const float* h0, const float* const*
         }
         p.wih1 = params[4]; p.bih1 = params[6];
         p.y[0] = saved + g.Y[0]; p.y[1] = y;
-        p.hN = hN; p.B = B; p.S = S; p.spin_limit = g_gru_spin_limit;
+        p.hN = hN; p.B = B; p.S = S; p.T = T; p.spin_limit = g_gru_spin_limit;
         p.first_sleep = g_gru_first_sleep[0];
         p.poll_plain = g_gru_poll_plain;
         p.xh[0] = p.xh[1] = nullptr;
@@ -1402,7 +1466,7 @@ static int gru_forward_impl(const float* x, const float* h0, const float* const*
             return 0;
         }
         const dim3 grid(kH / 16, cdiv(B, 16), 2);
-        for (int s = 0; s <= S; ++s) hipLaunchKernelGGL(gru2_fwd_kernel, grid, dim3(512), 0, st, p, s);
+        for (int s = 0; s <= T; ++s) hipLaunchKernelGGL(gru2_fwd_kernel, grid, dim3(512), 0, st, p, s);
         if (coef) launch_gru_coef(g, h0, saved, y, coef, B, S, st);
         CPC_LAUNCH_CHECK();
         return 0;
@@ -1495,12 +1559,24 @@ extern "C" int cpc_gru_backward_with_coef(const float* x, const float* h0, const
 // after `wgrad_stream`, and keeps `scratch` alive until then.  nl == 2 only; other depths run on `stream` alone.
 static int gru_backward_impl(const float* x, const float* h0, const float* const* params, const float* saved, const float* y,
                              const float* dy, const float* coef, float* scratch, float* dx, float* const* grads, int B, int S,
-                             int nl, void* stream, void* wgrad_stream, int D);
+                             int nl, void* stream, void* wgrad_stream, int D, int T = -1);
 extern "C" int cpc_gru_backward_streams(const float* x, const float* h0, const float* const* params,
                                         const float* saved, const float* y, const float* dy, const float* coef,
                                         float* scratch, float* dx, float* const* grads, int B, int S, int nl,
                                         void* stream, void* wgrad_stream) {
     return gru_backward_impl(x, h0, params, saved, y, dy, coef, scratch, dx, grads, B, S, nl, stream, wgrad_stream, kH);
+}
+// The same over the first T steps (1 <= T <= S; nl == 2): the caller promises dy[:, T:] == 0.  The recurrence then starts at
+// t = T - 1 with an incoming dh of zero -- exactly what the full run has at that step -- and writes the gate gradients of the steps
+// behind it as the zeros the full run computes there; every GEMM keeps its shape, so dx (dx[:, T:] == 0) and the eight gradients
+// are the full run's values.  T == S is cpc_gru_backward_streams.
+extern "C" int cpc_gru_backward_streams_steps(const float* x, const float* h0, const float* const* params,
+                                              const float* saved, const float* y, const float* dy, const float* coef,
+                                              float* scratch, float* dx, float* const* grads, int B, int S, int T, int nl,
+                                              void* stream, void* wgrad_stream) {
+    CPC_RETURN_IF(nl != 2, CPC_ERR_SHAPE);
+    CPC_RETURN_IF(T < 1 || T > S, CPC_ERR_ARG);
+    return gru_backward_impl(x, h0, params, saved, y, dy, coef, scratch, dx, grads, B, S, nl, stream, wgrad_stream, kH, T);
 }
 // D: x, dx (B,S,D), weight_ih_l0 and its gradient (3H,D): no prepared coefficients, one stream
 extern "C" int cpc_gru_backward_in(const float* x, const float* h0, const float* const* params, const float* saved, const float* y,
@@ -1510,10 +1586,12 @@ extern "C" int cpc_gru_backward_in(const float* x, const float* h0, const float*
 }
 static int gru_backward_impl(const float* x, const float* h0, const float* const* params, const float* saved, const float* y,
                              const float* dy, const float* coef, float* scratch, float* dx, float* const* grads, int B, int S,
-                             int nl, void* stream, void* wgrad_stream, int D) {
+                             int nl, void* stream, void* wgrad_stream, int D, int T) {
     GruLayout g;
     CPC_RETURN_IF(!gru_layout(B, S, nl, g, D), CPC_ERR_SHAPE);
     CPC_RETURN_IF(!x || !params || !saved || !scratch || !y || !dy || !dx || !grads, CPC_ERR_ARG);
+    if (T < 0) T = S;                                // (every entry but the _steps one)
+    CPC_RETURN_IF(T < 1 || T > S || (T != S && nl != 2), CPC_ERR_ARG);
     hipStream_t st = (hipStream_t)stream;
     hipStream_t wst = nl == 2 ? (hipStream_t)wgrad_stream : st;
     float* whhT = scratch + g.whhT, *wihT = scratch + g.wihT;
@@ -1529,7 +1607,7 @@ static int gru_backward_impl(const float* x, const float* h0, const float* const
         float* dGh_[2] = {scratch + g.dGh, scratch + g.dGh2};
         float* DH_[2] = {scratch + g.DH, scratch + g.DH2};
         Gru2Bwd p;
-        p.dy = dy; p.B = B; p.S = S; p.spin_limit = g_gru_spin_limit;
+        p.dy = dy; p.B = B; p.S = S; p.T = T; p.spin_limit = g_gru_spin_limit;
         p.first_sleep = g_gru_first_sleep[1];
         p.poll_plain = g_gru_poll_plain;                  // (narrowed below once the launch plan is known)
         const float* yl[2] = {saved + g.Y[0], y};
@@ -1577,7 +1655,12 @@ static int gru_backward_impl(const float* x, const float* h0, const float* const
             step_timer_mark(6, st);
         } else {
             const dim3 grid(kH / 16, cdiv(B, 16), 2);
-            for (int s = 0; s <= S; ++s) hipLaunchKernelGGL(gru2_bwd_kernel, grid, dim3(512), 0, st, p, s);
+            for (int l = 0; l < 2 && T < S; ++l) {         // (the persistent launch's gate waves write these zeros themselves)
+                launch_zero_tail(dGi_[l], B, S, T, kG, st);
+                launch_zero_tail(dGh_[l], B, S, T, kG, st);
+                launch_zero_tail(DH_[l], B, S, T, kH, st);
+            }
+            for (int s = 0; s <= T; ++s) hipLaunchKernelGGL(gru2_bwd_kernel, grid, dim3(512), 0, st, p, s);
         }
         CPC_LAUNCH_CHECK();
         // dx = dGi0 . W_ih0 first: it is what the rest of the backward pass waits for

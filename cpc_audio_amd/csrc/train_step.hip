@@ -22,6 +22,12 @@
 //   8  (with 1) the conv weight layouts / bounds of this step were prepared by cpc_train_step_tail at the end of the previous
 //      one; main waits for conv1's (event kEvNextConv1, recorded on the wgrad stream) in front of layer 1
 //  16  this step uses the second y0 buffer / bound set of the workspace (the caller alternates while it leaves tails open)
+//  32  (with 1, h0 == NULL) the caller reads neither hN nor c beyond step W - 1 (W = S - K, the steps the criterion reads): the forward
+//      recurrence runs W steps instead of S, c[:, W:] comes out zero and hN is not written.  (Taken up when |c| is bounded a priori,
+//      c_bound > 0; a measured bound would see the shortened c, so such a step runs all S steps and writes c and hN in full.)
+// The recurrence's BACKWARD runs over W steps in every phase mask: the step zeroes dc[:, W:] itself (cpc_nce_backward_prepare /
+// nce_gscale_kernel on every criterion setting; the dc GEMM writes window rows only), which is cpc_gru_backward_streams_steps' contract,
+// and the results are the full run's.
 #include "cpc_common.h"
 #include "cpc_internal.h"
 
@@ -142,8 +148,9 @@ extern "C" int cpc_train_step(const float* wave, const long* batchIdx, const lon
                               void* side_stream, void* prep_stream, void* wgrad_stream) {
     StepLayout s;
     CPC_RETURN_IF(!step_layout(B, L, K, N, s), CPC_ERR_SHAPE);
-    CPC_RETURN_IF(!wave || !params || !grads || !workspace || (phases & ~31) || !(phases & 3), CPC_ERR_ARG);
+    CPC_RETURN_IF(!wave || !params || !grads || !workspace || (phases & ~63) || !(phases & 3), CPC_ERR_ARG);
     CPC_RETURN_IF(((phases & 4) && !(phases & 2)) || ((phases & 8) && !(phases & 1)), CPC_ERR_ARG);
+    CPC_RETURN_IF((phases & 32) && (!(phases & 1) || h0 != nullptr), CPC_ERR_ARG);
     hipStream_t M = (hipStream_t)main_stream, S0 = (hipStream_t)side_stream, S1 = (hipStream_t)prep_stream,
                 S2 = (hipStream_t)wgrad_stream;
     // (equal handles are allowed: the launches then simply queue up in issue order, which respects every dependency below)
@@ -185,6 +192,7 @@ extern "C" int cpc_train_step(const float* wave, const long* batchIdx, const lon
         // S1 itself: the side stream reads the heads' weights and must come behind it -- long done by now)
         if (phases & 8) CPC_RETURN_IF(!wait(S0, pool[kEvNextRest]), CPC_ERR_ARG);
         const bool bounds_early = c_bound > 0.f;
+        const int Tf = (phases & 32) && bounds_early ? s.W : S;      // the forward recurrence's steps (bit 32)
         const bool early = bounds_early && !g_no_early;      // the criterion's operand bounds do not depend on c: its backward's weight-only share too
         auto prepare = [&]() -> int {      // index lists of the draws + operand bounds of the prediction GEMMs: depend on no activation
             int r = batchIdx ? cpc_nce_prepare(batchIdx, seqIdx, ext, perm, row_ptr, work, B, S, K, N, S0) : 0;
@@ -212,7 +220,8 @@ extern "C" int cpc_train_step(const float* wave, const long* batchIdx, const lon
         if (rc) return rc;
         // the hand-over buffers of the forward recurrence pre-filled beside the encoder instead of between the input projection
         // and the recurrence (queued behind the weight layouts: the recurrence is 0.4 ms away)
-        rc = cpc_gru_forward_prepare(ws + s.gru_fscr, B, S, 2, S1);
+        // (... and, for a forward over W steps, the zeros of the rows it leaves unwritten)
+        rc = cpc_gru_forward_prepare_steps(ws + s.gru_fscr, ws + s.gru_saved, c, B, S, Tf, 2, S1);
         if (rc) return rc;
         CPC_RETURN_IF(!rec(ev[7], S1), CPC_ERR_ARG);
         if (g_prep_point == 1 || g_prep_point == 3) {
@@ -232,7 +241,7 @@ extern "C" int cpc_train_step(const float* wave, const long* batchIdx, const lon
             CPC_RETURN_IF(!rec(ev[1], S0), CPC_ERR_ARG);
         }
         CPC_RETURN_IF(!wait(M, ev[7]), CPC_ERR_ARG);
-        rc = cpc_gru_forward_coef_prepared(z, h0, gru_p, ws + s.gru_saved, ws + s.gru_fscr, c, hN, coef, B, S, 2, M);
+        rc = cpc_gru_forward_coef_prepared_steps(z, h0, gru_p, ws + s.gru_saved, ws + s.gru_fscr, c, hN, coef, B, S, Tf, 2, M);
         if (rc) return rc;
         // what the recurrence's backward needs beyond the coefficients the forward writes on its way (weight transposes,
         // hand-over buffers: disjoint parts of `coef`) depends on the parameters only: beside the forward, on its own stream
@@ -260,8 +269,9 @@ extern "C" int cpc_train_step(const float* wave, const long* batchIdx, const lon
         CPC_RETURN_IF(!rec(ev[3], M) || !wait(M, ev[2]), CPC_ERR_ARG);
         // recurrence: dx on main, its weight / bias gradients straight into `grads` on the wgrad stream (no join here)
         const bool gru_wgrad_prep = g_gru_wgrad_prep && (phases & 3) == 3 && S1 != M && S1 != S2;
-        rc = cpc_gru_backward_streams(z, h0, gru_p, ws + s.gru_saved, c, dc, coef, ws + s.gru_bscr, dx, gru_g, B, S, 2, M,
-                                      gru_wgrad_prep ? S1 : S2);
+        // (over the W steps that carry a gradient: dc[:, W:] is the zero tail the criterion's preparation wrote)
+        rc = cpc_gru_backward_streams_steps(z, h0, gru_p, ws + s.gru_saved, c, dc, coef, ws + s.gru_bscr, dx, gru_g, B, S, s.W, 2, M,
+                                            gru_wgrad_prep ? S1 : S2);
         if (rc) return rc;
         if (gru_wgrad_prep) CPC_RETURN_IF(!rec(pool[kEvGruWgrad], S1), CPC_ERR_ARG);
         // ... and only now, with the persistent recurrence in flight (its 768-thread workgroups could not become resident beside

@@ -275,7 +275,8 @@ class CompositeStep:
             f["ready"] = None
             f["open"] = False                              # (ready: the call itself waits, in front of layer 1)
             f["main"] = main.cuda_stream
-            flags = (8 if ready else 0) | (16 if f["parity"] else 0)
+            # + 32: nobody reads hN (f["hN"] is scratch) or c beyond the criterion's window -- the forward recurrence stops there
+            flags = (8 if ready else 0) | (16 if f["parity"] else 0) | (0 if ar.keepHidden or h0 is not None else 32)
             tail = bool(open_tail) and not self.allreduce._active() and not torch.cuda.is_current_stream_capturing()
             f["tail"] = False
 

@@ -318,6 +318,23 @@ int cpc_gru_backward_streams(const float* x, const float* h0, const float* const
                              const float* y, const float* dy, const float* coef, float* scratch, float* dx,
                              float* const* grads, int B, int S, int nl, void* stream, void* wgrad_stream);
 
+/* The two-layer recurrence over the first T of S steps (1 <= T <= S, else CPC_ERR_ARG; nl == 2): for a loss that reads y[:, :T] only.
+ * S stays the stride of every tensor and the M of every GEMM; T only bounds the time loops, each of which costs a hand-over
+ * round trip between workgroups.  T == S is exactly the entry without the suffix.
+ *   cpc_gru_forward_prepare_steps: cpc_gru_forward_prepare, plus zeros in rows t >= T of y and of layer 0's output in `saved`
+ *     (what the shortened forward leaves unwritten and the backward's GEMMs read over all S steps); any stream.
+ *   cpc_gru_forward_coef_prepared_steps: runs steps t < T; y[:, :T], the saved values and the coefficients of those steps are the
+ *     full run's bits.  hN is written only when T == S.  Only a backward with the same T (or a smaller one) may follow.
+ *   cpc_gru_backward_streams_steps: the caller promises dy[:, T:] == 0.  Starts at t = T - 1 with an incoming dh of zero -- what
+ *     the full run has there -- and writes the gate gradients of the steps behind as zeros: dx (dx[:, T:] == 0) and the eight
+ *     gradients equal cpc_gru_backward_streams' on the same inputs. */
+int cpc_gru_forward_prepare_steps(float* scratch, float* saved, float* y, int B, int S, int T, int nl, void* stream);
+int cpc_gru_forward_coef_prepared_steps(const float* x, const float* h0, const float* const* params, float* saved, float* scratch,
+                                        float* y, float* hN, float* coef, int B, int S, int T, int nl, void* stream);
+int cpc_gru_backward_streams_steps(const float* x, const float* h0, const float* const* params, const float* saved,
+                                   const float* y, const float* dy, const float* coef, float* scratch, float* dx,
+                                   float* const* grads, int B, int S, int T, int nl, void* stream, void* wgrad_stream);
+
 /* ------------------------------------------------------------ LSTM autoregressor ----
  * CPCAR with mode "LSTM" (cpc/model.py:167-169, the reference's default --arMode): nn.LSTM(256, 256, num_layers=nl,
  * batch_first=True), 1 <= nl <= 8, fp32, optional carried state (h0, c0) -- both or neither.
@@ -920,7 +937,12 @@ int cpc_nce_wide_backward(const float* pred, const float* z, const int* ext, con
  *     rest on prep_stream (cpc_adam_step three times, cpc_train_step_wait for their gradients), calls cpc_train_step_tail, and gives
  *     the NEXT step + 8 (its weight layouts are ready; main_stream waits for conv1's in front of layer 1) and alternates + 16
  *     (second y0 buffer / bound set of the workspace: the next layer 0 runs while layer 1's weight gradient still reads y0).
- *   A caller that touches parameters or gradients outside these calls first joins with cpc_train_step_wait(main, 2, main). */
+ *   A caller that touches parameters or gradients outside these calls first joins with cpc_train_step_wait(main, 2, main).
+ *   + 32 (with 1; h0 must be NULL, else CPC_ERR_ARG): the caller reads neither hN nor c beyond step W - 1, W = S - K -- the steps
+ *     the criterion reads.  The forward recurrence then runs W steps instead of S: c[:, W:] is zero and hN is NOT written.  Losses,
+ *     accuracies, z, c[:, :W] and every gradient are those of the step without the bit.  (Taken up with c_bound > 0; with a
+ *     measured bound the step runs all S steps.)  The recurrence's backward runs over W steps in every mask: dc[:, W:] is zero by
+ *     construction, and the results are the full run's. */
 int cpc_train_step_layout(int B, int L, int K, int N, long* sizes);
 int cpc_train_step(const float* wave, const long* batchIdx, const long* seqIdx, const float* h0, float c_bound,
                    const float* const* params, float* const* grads, const float* gloss, float* workspace, float* losses,
