@@ -156,10 +156,15 @@ SIGNATURES = {
     "cpc_phone_head_layout": (_I, [_I, _I, _I, _I, _P]),
     "cpc_phone_head_forward": (_I, [_P] * 6 + [_I, _I, _I, _P]),
     "cpc_phone_head_backward": (_I, [_P] * 7 + [_I, _I, _I, _P]),
+    "cpc_phone_head_layout_d": (_I, [_I, _I, _I, _I, _I, _P]),
+    "cpc_phone_head_forward_d": (_I, [_P] * 6 + [_I, _I, _I, _I, _P]),
+    "cpc_phone_head_backward_d": (_I, [_P] * 7 + [_I, _I, _I, _I, _P]),
     "cpc_ctc_seq_forward": (_I, [_P, _P, _P, _L, _P, _P, _P] + [_I] * 6 + [_P]),
     "cpc_ctc_seq_backward": (_I, [_P] * 4 + [_I] * 6 + [_P]),
     "cpc_seqnorm_forward": (_I, [_P] * 5 + [_I, _I, _I, _P]),
     "cpc_seqnorm_backward": (_I, [_P] * 6 + [_I, _I, _I, _P]),
+    "cpc_seqnorm_forward_d": (_I, [_P] * 5 + [_I, _I, _I, _I, _P]),
+    "cpc_seqnorm_backward_d": (_I, [_P] * 6 + [_I, _I, _I, _I, _P]),
     "cpc_lfb_layout": (_I, [_I, _I, _I, _P]),
     "cpc_lfb_energy_forward": (_I, [_P] * 6 + [_I, _I, _I, _P]),
     "cpc_lfb_energy_backward": (_I, [_P] * 8 + [_I, _I, _I, _P]),
@@ -178,6 +183,7 @@ SIGNATURES = {
     "cpc_probe_train_step_d": (_I, [_P, _L, _P, _I, _I, _I] + [_P] * 6 + [ctypes.c_double] * 6 + [_P] * 7),
     "cpc_probe_eval_d": (_I, [_P, _L, _P, _I, _I, _I] + [_P] * 7),
     "cpc_posterior_forward": (_I, [_P, _L, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "cpc_posterior_forward_d": (_I, [_P, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "cpc_abx_layout": (_I, [_I, _I, _I, _L, _P]),
     "cpc_abx_group_scores": (_I, [_P, _P, _P, _I, _L, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P]),
     "cpc_abx_pair_dtw": (_I, [_P, _P, _P, _I, _L, _I, _I, _I, _P, _I, _P, _P]),

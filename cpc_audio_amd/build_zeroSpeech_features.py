@@ -8,7 +8,8 @@ saved in the same checkpoint (train --supervised, linear_separability --pathPhon
 ``.npy``.  Arguments, defaults and the files written are the reference's; the arrayfire format is not offered.
 
 Files are read through dataset.loadFile and cut into chunks by harness.build_feature; the classifier with its softmax -- or
-argmax and one-hot -- is one HIP call per chunk batch (harness.ModelPhoneCombined, csrc/posterior.hip; --hipHead / --no-hipHead).
+argmax and one-hot -- is one HIP call per chunk batch (harness.ModelPhoneCombined, csrc/posterior.hip; --hipHead / --no-hipHead)
+on 256 features and, with --wideKernel, on any width from 1 to 512 (an MFCC, filter-bank, no_ar or hiddenGar 512 checkpoint).
 
 Two defects of the reference script are not reproduced: --addCriterion works here (the reference passes ModelPhoneCombined one
 argument too many and raises TypeError), and --oneHot --seqNorm, which fails there inside the mean of an int64 tensor, is
@@ -79,6 +80,8 @@ def parse_args(argv):
                              "(default: where it applies)")
     parser.add_argument('--no-hipHead', dest='hipHead', action='store_false',
                         help="With --addCriterion: the classifier and its softmax / one-hot as torch ops")
+    parser.add_argument('--wideKernel', action='store_true', default=argparse.SUPPRESS,
+                        help="With --addCriterion: the HIP call at any feature width from 1 to 512 (off by default: 256 only)")
     return parser.parse_args(argv)
 
 
@@ -102,7 +105,8 @@ def main(argv):
     featureMaker = FeatureModule(model, args.getEncoded)
     if args.addCriterion:
         criterion, _ = loadSupervisedCriterion(args.pathCheckpoint)
-        featureMaker = ModelPhoneCombined(featureMaker, criterion, args.oneHot, hipHead=args.hipHead)
+        featureMaker = ModelPhoneCombined(featureMaker, criterion, args.oneHot, hipHead=args.hipHead,
+                                          wideKernel=getattr(args, "wideKernel", False))
     featureMaker = featureMaker.cuda()
     if not args.train_mode:
         featureMaker.eval()

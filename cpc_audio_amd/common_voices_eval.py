@@ -20,7 +20,8 @@ lengths -- run on csrc/phone_head.hip (ops.PhoneHeadCtcFunction, ops.phone_head_
 CTCphone_criterion).  What stands in front of the head -- seqNorm, the optional LSTM and the dropout -- runs on
 csrc/seqnorm.hip and csrc/lstm.hip with `--hipFront` (ops.SeqNormFunction, ops.LstmFunction: no host synchronisation, no
 per-utterance launches) and as torch GPU ops without it (the default); the whole classifier is torch ops for another feature
-width or kernel size.  CPC checkpoints load as abx.py loads them (checkpoint_args.json next to the checkpoint,
+width or kernel size -- unless `--wideKernel` is given, with which head and front run on the same kernels at any width from 1
+to 512 (only the `--LSTM` recurrence, whose hidden width follows the features, stays on nn.LSTM away from 256).  CPC checkpoints load as abx.py loads them (checkpoint_args.json next to the checkpoint,
 harness.load_checkpoint); their encoder and autoregressor run on the package's HIP kernels.
 """
 import argparse
@@ -132,23 +133,34 @@ class CTCphone_criterion(torch.nn.Module):
     parameters).  It takes dimEncoder 256 and CUDA fp32 features.  None: HIP_FRONT_DEFAULT (off); False: the torch ops; True:
     the HIP front or NotImplementedError.  The dropout's factors come from torch's generator (bernoulli_(0.5) * 2: the
     distribution of nn.Dropout2d on (B, 256, S), not its bits) and stay in last_channel_scale; last_front names the front of
-    the last call ("hip", "torch", None when no front op was active)."""
+    the last call ("hip", "torch", None when no front op was active).
+
+    wideKernel (off by default): the HIP head and the HIP front at any dimEncoder from 1 to 512 (cpc_phone_head_*_d,
+    cpc_seqnorm_*_d); sizeKernel is still 8, and hipHead and hipFront keep their three meanings.  The LSTM is nn.LSTM(dimEncoder,
+    dimEncoder): its hidden width follows dimEncoder, and csrc/lstm.hip's recurrence is 256 wide.  So away from 256 the HIP
+    front is the HIP seqNorm, then nn.LSTM (MIOpen), then the HIP dropout scale; last_front stays "hip" and last_lstm names the
+    recurrence's path of the last call ("hip", "torch", None without --LSTM or when no front op was active)."""
 
     def __init__(self, dimEncoder, nPhones, LSTM=False, sizeKernel=8, seqNorm=False, dropout=False, reduction='sum',
-                 hipHead=None, hipFront=None):
+                 hipHead=None, hipFront=None, wideKernel=False):
         super().__init__()
         self.hipHead = hipHead
         self.hipFront = hipFront
-        self._hipConfig = dimEncoder == 256 and sizeKernel == ops.PHONE_HEAD_KERNEL
+        self.wideKernel = bool(wideKernel)
+        widths = f"1 <= dimEncoder <= {ops.PHONE_HEAD_MAX_DIM}" if self.wideKernel else "dimEncoder 256"
+        width_ok = 1 <= dimEncoder <= ops.PHONE_HEAD_MAX_DIM if self.wideKernel else dimEncoder == 256
+        self._hipConfig = width_ok and sizeKernel == ops.PHONE_HEAD_KERNEL
         if hipHead and not self._hipConfig:
-            raise NotImplementedError("CTCphone_criterion(hipHead=True): the HIP phone head is built for dimEncoder 256 and "
+            raise NotImplementedError(f"CTCphone_criterion(hipHead=True): the HIP phone head is built for {widths} and "
                                       f"sizeKernel 8 (got {dimEncoder}, {sizeKernel})")
-        self._hipFrontConfig = dimEncoder == 256
+        self._hipFrontConfig = width_ok
         if hipFront and not self._hipFrontConfig:
             raise NotImplementedError("CTCphone_criterion(hipFront=True): the HIP seqNorm, LSTM and dropout are built for "
-                                      f"dimEncoder 256 (got {dimEncoder})")
+                                      f"{widths} (got {dimEncoder})")
+        self._hipLstmConfig = dimEncoder == 256            # csrc/lstm.hip: a recurrence 256 wide
         self.last_path = None
         self.last_front = None
+        self.last_lstm = None
         self.last_channel_scale = None
         self.seqNorm = seqNorm
         self.epsilon = 1e-8
@@ -164,9 +176,9 @@ class CTCphone_criterion(torch.nn.Module):
         """Does this call run on the HIP head?"""
         if self.hipHead is False or (self.hipHead is None and not HIP_HEAD_DEFAULT) or not self._hipConfig:
             return False
-        B, S, _ = cFeature.size()
+        B, S, D = cFeature.size()
         ok = cFeature.is_cuda and cFeature.dtype == torch.float32 and \
-            ops.phone_head_supported(B, S, self.BLANK_LABEL + 1, Lmax)
+            ops.phone_head_supported(B, S, self.BLANK_LABEL + 1, Lmax, D)
         if self.hipHead and not ok:
             raise NotImplementedError("CTCphone_criterion(hipHead=True): the HIP phone head takes CUDA fp32 features of a shape "
                                       f"cpc_phone_head_layout accepts (got {tuple(cFeature.size())}, {cFeature.dtype}, "
@@ -177,9 +189,9 @@ class CTCphone_criterion(torch.nn.Module):
         """Does this call run its seqNorm, LSTM and dropout on the HIP kernels?"""
         if self.hipFront is False or (self.hipFront is None and not HIP_FRONT_DEFAULT) or not self._hipFrontConfig:
             return False
-        B, S, _ = cFeature.size()
-        ok = cFeature.is_cuda and cFeature.dtype == torch.float32 and ops.seqnorm_supported(B, S) and \
-            (not self.useLSTM or ops.lstm_supported(B, S))
+        B, S, D = cFeature.size()
+        ok = cFeature.is_cuda and cFeature.dtype == torch.float32 and ops.seqnorm_supported(B, S, D) and \
+            (not self.useLSTM or not self._hipLstmConfig or ops.lstm_supported(B, S))
         if self.hipFront and not ok:
             raise NotImplementedError("CTCphone_criterion(hipFront=True): the HIP front takes CUDA fp32 features of a shape "
                                       f"cpc_seqnorm_forward and cpc_lstm_layout accept (got {tuple(cFeature.size())}, "
@@ -191,6 +203,7 @@ class CTCphone_criterion(torch.nn.Module):
         B, S, H = cFeature.size()
         drop = self.dropout is not None and self.training
         self.last_channel_scale = None
+        self.last_lstm = None
         if not (self.seqNorm or self.useLSTM or drop):
             self.last_front = None
             return cFeature
@@ -200,9 +213,13 @@ class CTCphone_criterion(torch.nn.Module):
             self.last_channel_scale = scale
             if self.seqNorm:                       # the dropout rides on the normalisation unless the LSTM stands between
                 cFeature = ops.SeqNormFunction.apply(cFeature, featureSize, None if self.useLSTM else scale, True)
-            if self.useLSTM:
+            if self.useLSTM and self._hipLstmConfig:
+                self.last_lstm = "hip"
                 cFeature = ops.LstmFunction.apply(cFeature, None, False, self.conv1.weight_ih_l0, self.conv1.weight_hh_l0,
                                                   self.conv1.bias_ih_l0, self.conv1.bias_hh_l0)[0]
+            elif self.useLSTM:                     # a hidden width other than 256: the one piece that stays on MIOpen
+                self.last_lstm = "torch"
+                cFeature = self.conv1(cFeature)[0]
             if drop and (self.useLSTM or not self.seqNorm):
                 cFeature = ops.SeqNormFunction.apply(cFeature, None, scale, False)
             return cFeature
@@ -216,6 +233,7 @@ class CTCphone_criterion(torch.nn.Module):
                 rows.append((cFeature[b] - m) / torch.sqrt(v + self.epsilon))
             cFeature = torch.stack(rows)
         if self.useLSTM:
+            self.last_lstm = "torch"
             cFeature = self.conv1(cFeature)[0]
         if self.dropout is not None:
             cFeature = self.dropout(cFeature.permute(0, 2, 1)).permute(0, 2, 1)
@@ -399,6 +417,8 @@ def get_PER_args(args):
     args.loss_reduction = data.get("loss_reduction", "mean")
     args.hipHead = data.get("hipHead", None)
     args.hipFront = data.get("hipFront", None)
+    if data.get("wideKernel", False):                      # (absent where the training run did not ask for it)
+        args.wideKernel = True
     return args
 
 
@@ -436,6 +456,9 @@ def parse_args(argv):
                    help="The classifier's seqNorm, LSTM and dropout on the HIP kernels (an error where they do not apply)")
     t.add_argument('--no-hipFront', dest='hipFront', action='store_false',
                    help="The classifier's seqNorm, LSTM and dropout as torch ops (the default)")
+    t.add_argument('--wideKernel', action='store_true', default=argparse.SUPPRESS,
+                   help="The HIP head and the HIP front at any feature width from 1 to 512 (off by default: 256 only); per reads "
+                   "it back from the training run's arguments")
     p = sub.add_parser('per')
     p.add_argument('output', type=str)
     p.add_argument('--batchSize', type=int, default=8)
@@ -519,7 +542,8 @@ def _main(args):
     feature_maker, hidden_gar, downsampling_factor = load_feature_maker(args.pathCheckpoint, args.no_pretraining, args.in_dim)
     feature_maker.cuda()
     phone_criterion = CTCphone_criterion(hidden_gar, n_phones, args.LSTM, seqNorm=args.seqNorm, dropout=args.dropout,
-                                         reduction=args.loss_reduction, hipHead=args.hipHead, hipFront=args.hipFront).cuda()
+                                         reduction=args.loss_reduction, hipHead=args.hipHead, hipFront=args.hipFront,
+                                         wideKernel=getattr(args, "wideKernel", False)).cuda()
     print(f"Loading the validation dataset at {args.pathDB}")
     dataset_val = SingleSequenceDataset(args.pathDB, seq_val, phone_labels, inDim=args.in_dim)
     val_loader = DataLoader(dataset_val, batch_size=args.batchSize, shuffle=True)

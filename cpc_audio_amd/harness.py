@@ -395,11 +395,14 @@ class ModelPhoneCombined(torch.nn.Module):
     PhoneCriterion whose classifier is a single nn.Linear, or a CTCPhoneCriterion, with 256 input features and 2..8192 classes,
     and CUDA fp32 features with unit last stride.  None: use it where it applies (POSTERIOR_HIP_DEFAULT), torch elsewhere;
     False: torch; True: the HIP call or NotImplementedError.  Evaluation only: the HIP path is not differentiable.
-    ``last_path`` names the path of the last call ("hip" / "torch")."""
+    ``last_path`` names the path of the last call ("hip" / "torch").
+    wideKernel (off by default): the HIP call at any feature width from 1 to 512 that is the classifier's in_features
+    (ops.posterior(..., wide=True): cpc_posterior_forward_d)."""
 
-    def __init__(self, model, criterion, oneHot, hipHead=None):
+    def __init__(self, model, criterion, oneHot, hipHead=None, wideKernel=False):
         super().__init__()
         self.model, self.criterion, self.oneHot, self.hipHead = model, criterion, oneHot, hipHead
+        self.wideKernel = bool(wideKernel)
         self.last_path = None
 
     @property
@@ -420,12 +423,14 @@ class ModelPhoneCombined(torch.nn.Module):
             return None
         lin = getattr(self.criterion, "PhoneCriterionClassifier", None)
         ok = isinstance(self.criterion, (PhoneCriterion, CTCPhoneCriterion)) and isinstance(lin, torch.nn.Linear) \
-            and lin.in_features == 256 and 2 <= lin.out_features <= ops.POSTERIOR_MAX_CLASSES \
-            and c.dim() == 3 and c.size(2) == 256 and c.is_cuda and c.dtype == torch.float32 and c.stride(2) == 1 \
+            and (1 <= lin.in_features <= ops.PHONE_HEAD_MAX_DIM if self.wideKernel else lin.in_features == 256) \
+            and 2 <= lin.out_features <= ops.POSTERIOR_MAX_CLASSES \
+            and c.dim() == 3 and c.size(2) == lin.in_features and c.is_cuda and c.dtype == torch.float32 and c.stride(2) == 1 \
             and lin.weight.device == c.device
         if self.hipHead and not ok:
             raise NotImplementedError("ModelPhoneCombined(hipHead=True): the HIP posterior call takes a single-nn.Linear "
-                                      "PhoneCriterion or a CTCPhoneCriterion on 256 features with 2..8192 classes and CUDA fp32 "
+                                      f"PhoneCriterion or a CTCPhoneCriterion on {'1..512' if self.wideKernel else '256'} features with 2..8192 "
+                                      "classes and CUDA fp32 "
                                       f"features (got {type(self.criterion).__name__}, {tuple(c.size())}, {c.dtype}, {c.device})")
         return lin if ok else None
 
@@ -436,7 +441,7 @@ class ModelPhoneCombined(torch.nn.Module):
             self.last_path = "hip"
             B, S, H = c_feature.size()
             rows = c_feature.reshape(B * S, H)            # (a view wherever the frames are evenly strided)
-            return ops.posterior(rows, lin.weight, lin.bias, one_hot=self.oneHot).view(B, S, -1)
+            return ops.posterior(rows, lin.weight, lin.bias, one_hot=self.oneHot, wide=self.wideKernel).view(B, S, -1)
         self.last_path = "torch"
         pred = self.criterion.getPrediction(c_feature)
         if self.oneHot:

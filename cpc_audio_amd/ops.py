@@ -917,61 +917,81 @@ PHONE_HEAD_KERNEL, PHONE_HEAD_STRIDE = 8, 4
 _CTC_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
 
 
-def phone_head_layout(B, S, C, Lmax=0):
-    """(T, wr floats, scratch floats, logits floats, CTC saved floats) of cpc_phone_head_layout; ValueError for a shape the
-    kernels do not take."""
-    return _layout("phone_head_layout", _lib.get().cpc_phone_head_layout, 5, int(B), int(S), int(C), int(Lmax))
+PHONE_HEAD_MAX_DIM = 512      # widest feature row of cpc_phone_head_*_d, cpc_seqnorm_*_d and cpc_posterior_forward_d
 
 
-def phone_head_supported(B, S, C, Lmax=0):
+def _width_checked(D, what):
+    if not 1 <= int(D) <= PHONE_HEAD_MAX_DIM:
+        raise NotImplementedError(f"cpc_audio_amd.{what}: the HIP kernels take 1 to {PHONE_HEAD_MAX_DIM} input features, got {D}")
+    return int(D)
+
+
+def phone_head_layout(B, S, C, Lmax=0, D=_HID):
+    """(T, wr floats, scratch floats, logits floats, CTC saved floats) of cpc_phone_head_layout (D = 256) or
+    cpc_phone_head_layout_d (any other D in 1..512; NotImplementedError beyond); ValueError for a shape the kernels do not take."""
+    if D == _HID:
+        return _layout("phone_head_layout", _lib.get().cpc_phone_head_layout, 5, int(B), int(S), int(C), int(Lmax))
+    D = _width_checked(D, "phone_head_layout")
+    return _layout("phone_head_layout_d", _lib.get().cpc_phone_head_layout_d, 5, int(B), int(S), int(C), int(Lmax), D)
+
+
+def phone_head_supported(B, S, C, Lmax=0, D=_HID):
     try:
-        phone_head_layout(B, S, C, Lmax)
-    except ValueError:
+        phone_head_layout(B, S, C, Lmax, D)
+    except (ValueError, NotImplementedError):
         return False
     return True
 
 
 def _phone_head_inputs(x, weight, what):
+    """The contiguous features; their width D is the weight's (ValueError otherwise) and lies in 1..512."""
+    if x.dim() != 3 or weight.dim() != 3 or weight.shape[2] != PHONE_HEAD_KERNEL:
+        raise NotImplementedError(f"cpc_audio_amd.{what}: the HIP phone head is built for (B, S, D) features and a "
+                                  "(C, D, 8) weight")
+    if x.shape[2] != weight.shape[1]:
+        raise ValueError(f"{what}: features of shape {tuple(x.shape)} for a weight of shape {tuple(weight.shape)}")
+    _width_checked(x.shape[2], what)
     _require_cuda(x, what)
-    if x.dim() != 3 or x.shape[2] != _HID or weight.dim() != 3 or tuple(weight.shape[1:]) != (_HID, PHONE_HEAD_KERNEL):
-        raise NotImplementedError(f"cpc_audio_amd.{what}: the HIP phone head is built for (B, S, 256) features and a "
-                                  "(C, 256, 8) weight")
     return x.contiguous()
 
 
 def _phone_head_forward(x, weight, bias, sizes):
     lib = _lib.get()
-    B, S, _ = x.shape
+    B, S, D = x.shape
     C = weight.shape[0]
     wr = torch.empty(sizes[1], device=x.device, dtype=torch.float32)
     scratch = torch.empty(sizes[2], device=x.device, dtype=torch.float32)
     logits = torch.empty(B, sizes[0], C, device=x.device, dtype=torch.float32)
-    lib.check(lib.cpc_phone_head_forward(_p(x), _p(weight), _p(bias), _p(wr), _p(scratch), _p(logits), B, S, C, _stream()),
-              "phone_head_forward")
+    args = (_p(x), _p(weight), _p(bias), _p(wr), _p(scratch), _p(logits), B, S, C)
+    if D == _HID:
+        lib.check(lib.cpc_phone_head_forward(*args, _stream()), "phone_head_forward")
+    else:
+        lib.check(lib.cpc_phone_head_forward_d(*args, D, _stream()), "phone_head_forward_d")
     return logits, wr
 
 
 def phone_head_logits(x, weight, bias):
-    """x (B, S, 256) channels-last, weight (C, 256, 8), bias (C) -> logits (B, (S - 8) // 4 + 1, C): nn.Conv1d(256, C, 8,
-    stride 4) of the permuted features, permuted back.  Not differentiable (evaluation: val_step, perStep)."""
+    """x (B, S, D) channels-last, weight (C, D, 8), bias (C), 1 <= D <= 512 -> logits (B, (S - 8) // 4 + 1, C): nn.Conv1d(D, C,
+    8, stride 4) of the permuted features, permuted back.  256 features go to the 256 entry points, any other width to the _d
+    ones.  Not differentiable (evaluation: val_step, perStep)."""
     x = _phone_head_inputs(x.detach(), weight, "phone_head_logits")
     weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
     with torch.cuda.device(x.device):
-        sizes = phone_head_layout(x.shape[0], x.shape[1], weight.shape[0])
+        sizes = phone_head_layout(x.shape[0], x.shape[1], weight.shape[0], 0, x.shape[2])
         return _phone_head_forward(x, weight, bias, sizes)[0]
 
 
 class PhoneHeadCtcFunction(torch.autograd.Function):
-    """x (B, S, 256), weight (C, 256, 8), bias (C), in_len (B) int64 windows per utterance, targets (B, Lmax) int64 padded,
-    tgt_len (B) int64, blank, reduction -> loss (1,) float32 ((B,) for 'none'): nn.Conv1d(256, C, 8, stride 4), log_softmax
-    and nn.CTCLoss(blank, reduction, zero_infinity=True).  Lengths and targets stay on the device.  x receives a gradient
-    only when it requires one."""
+    """x (B, S, D), weight (C, D, 8), bias (C), in_len (B) int64 windows per utterance, targets (B, Lmax) int64 padded,
+    tgt_len (B) int64, blank, reduction -> loss (1,) float32 ((B,) for 'none'): nn.Conv1d(D, C, 8, stride 4), log_softmax
+    and nn.CTCLoss(blank, reduction, zero_infinity=True), 1 <= D <= 512 (256: the 256 entry points, otherwise the _d ones).
+    Lengths and targets stay on the device.  x receives a gradient only when it requires one."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, in_len, targets, tgt_len, blank, reduction):
         x = _phone_head_inputs(x, weight, "PhoneHeadCtcFunction")
         lib = _lib.get()
-        B, S, _ = x.shape
+        B, S, D = x.shape
         C = weight.shape[0]
         red = _CTC_REDUCTIONS[reduction]
         targets = targets.to(x.device, non_blocking=True)
@@ -987,7 +1007,7 @@ class PhoneHeadCtcFunction(torch.autograd.Function):
             raise ValueError(f"PhoneHeadCtcFunction: {in_len.numel()} input and {tgt_len.numel()} target lengths for {B} utterances")
         weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
         with torch.cuda.device(x.device):
-            sizes = phone_head_layout(B, S, C, Lmax)
+            sizes = phone_head_layout(B, S, C, Lmax, D)
             T = sizes[0]
             logits, wr = _phone_head_forward(x, weight, bias, sizes)
             saved = torch.empty(sizes[4], device=x.device, dtype=torch.float32)
@@ -1011,11 +1031,15 @@ class PhoneHeadCtcFunction(torch.autograd.Function):
             lib.check(lib.cpc_ctc_seq_backward(_p(logits), _p(saved), _p(dloss.contiguous()), _p(dlogits), B, T, C, Lmax, blank,
                                                red, _stream()), "ctc_seq_backward")
             scratch = torch.empty(nscr, device=x.device, dtype=torch.float32)
-            dW = torch.empty(C, _HID, PHONE_HEAD_KERNEL, device=x.device, dtype=torch.float32)
+            D = x.shape[2]
+            dW = torch.empty(C, D, PHONE_HEAD_KERNEL, device=x.device, dtype=torch.float32)
             db = torch.empty(C, device=x.device, dtype=torch.float32)
             dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-            lib.check(lib.cpc_phone_head_backward(_p(x), _p(wr), _p(dlogits), _p(scratch), _p(dW), _p(db), _p(dx), B, S, C,
-                                                  _stream()), "phone_head_backward")
+            args = (_p(x), _p(wr), _p(dlogits), _p(scratch), _p(dW), _p(db), _p(dx), B, S, C)
+            if D == _HID:
+                lib.check(lib.cpc_phone_head_backward(*args, _stream()), "phone_head_backward")
+            else:
+                lib.check(lib.cpc_phone_head_backward_d(*args, D, _stream()), "phone_head_backward_d")
         return dx, dW, db, None, None, None, None, None
 
 
@@ -1085,25 +1109,28 @@ class PredConvFunction(torch.autograd.Function):
 
 
 # ---- the PER phone classifier's front: seqNorm and dropout (csrc/seqnorm.hip) ------------------------------------------
-def seqnorm_supported(B, S):
-    """The shapes cpc_seqnorm_forward takes: B >= 1, S >= 1, B * S * 256 < 2^31."""
-    return B >= 1 and S >= 1 and B * S * _HID < (1 << 31)
+def seqnorm_supported(B, S, D=_HID):
+    """The shapes cpc_seqnorm_forward (D = 256) and cpc_seqnorm_forward_d take: B >= 1, S >= 1, 1 <= D <= 512, B * S * D < 2^31."""
+    return B >= 1 and S >= 1 and 1 <= D <= PHONE_HEAD_MAX_DIM and B * S * D < (1 << 31)
 
 
 class SeqNormFunction(torch.autograd.Function):
-    """x (B, S, 256), lengths (B) int64 valid frames per utterance or None (all S), scale (B, 256) or None, normalise ->
-    y (B, S, 256): per utterance and channel, (x - mean) / sqrt(var + 1e-8) with the mean and the unbiased variance of the
+    """x (B, S, D), 1 <= D <= 512 (256: the 256 entry points, otherwise the _d ones), lengths (B) int64 valid frames per
+    utterance or None (all S), scale (B, D) or None, normalise -> y (B, S, D): per utterance and channel, (x - mean) / sqrt(var + 1e-8) with the mean and the unbiased variance of the
     valid frames, applied to every frame, times scale (CTCphone_criterion's seqNorm with Dropout2d's per-channel factor);
     normalise False: x * scale.  The lengths stay on the device.  Neither lengths nor scale receives a gradient; when x does
     not require one, no statistics are kept and backward launches nothing.  x is never written."""
 
     @staticmethod
     def forward(ctx, x, lengths, scale, normalise):
+        if x.dim() != 3:
+            raise NotImplementedError("cpc_audio_amd.SeqNormFunction: built for (B, S, D) features")
+        if scale is not None and (scale.dim() != 2 or scale.shape[1] != x.shape[2]):
+            raise ValueError(f"SeqNormFunction: scale of shape {tuple(scale.shape)} for features of shape {tuple(x.shape)}")
+        _width_checked(x.shape[2], "SeqNormFunction")
         _require_cuda(x, "SeqNormFunction")
-        if x.dim() != 3 or x.shape[2] != _HID:
-            raise NotImplementedError("cpc_audio_amd.SeqNormFunction: built for (B, S, 256) features")
         lib = _lib.get()
-        B, S, _ = x.shape
+        B, S, D = x.shape
         x = x.contiguous()
         normalise = bool(normalise)
         if lengths is not None:
@@ -1112,15 +1139,18 @@ class SeqNormFunction(torch.autograd.Function):
                 raise ValueError(f"SeqNormFunction: {lengths.numel()} lengths for {B} utterances")
         if scale is not None:
             _require_cuda(scale, "SeqNormFunction")
-            if tuple(scale.shape) != (B, _HID):
+            if tuple(scale.shape) != (B, D):
                 raise ValueError(f"SeqNormFunction: scale of shape {tuple(scale.shape)} for {B} utterances")
             scale = scale.detach().contiguous()
         need_dx = ctx.needs_input_grad[0]
         with torch.cuda.device(x.device):
             y = torch.empty_like(x)
-            stats = torch.empty(B, 2, _HID, device=x.device, dtype=torch.float32) if need_dx and normalise else None
-            lib.check(lib.cpc_seqnorm_forward(_p(x), _p(lengths), _p(scale), _p(y), _p(stats), B, S, int(normalise), _stream()),
-                      "seqnorm_forward")
+            stats = torch.empty(B, 2, D, device=x.device, dtype=torch.float32) if need_dx and normalise else None
+            args = (_p(x), _p(lengths), _p(scale), _p(y), _p(stats), B, S)
+            if D == _HID:
+                lib.check(lib.cpc_seqnorm_forward(*args, int(normalise), _stream()), "seqnorm_forward")
+            else:
+                lib.check(lib.cpc_seqnorm_forward_d(*args, D, int(normalise), _stream()), "seqnorm_forward_d")
         if need_dx:
             ctx.save_for_backward(*(t for t in (x if normalise else None, lengths, scale, stats) if t is not None))
             ctx.have = (normalise, lengths is not None, scale is not None)
@@ -1138,11 +1168,14 @@ class SeqNormFunction(torch.autograd.Function):
         stats = saved.pop(0) if normalise else None
         lib = _lib.get()
         dy = dy.contiguous()
-        B, S, _ = dy.shape
+        B, S, D = dy.shape
         with torch.cuda.device(dy.device):
             dx = torch.empty_like(dy)
-            lib.check(lib.cpc_seqnorm_backward(_p(x), _p(dy), _p(lengths), _p(scale), _p(stats), _p(dx), B, S, int(normalise),
-                                               _stream()), "seqnorm_backward")
+            args = (_p(x), _p(dy), _p(lengths), _p(scale), _p(stats), _p(dx), B, S)
+            if D == _HID:
+                lib.check(lib.cpc_seqnorm_backward(*args, int(normalise), _stream()), "seqnorm_backward")
+            else:
+                lib.check(lib.cpc_seqnorm_backward_d(*args, D, int(normalise), _stream()), "seqnorm_backward_d")
         return dx, None, None, None
 
 
@@ -1384,24 +1417,33 @@ POSTERIOR_MAX_CLASSES = 8192
 
 
 @torch.no_grad()
-def posterior(x, weight, bias, one_hot=False):
+def posterior(x, weight, bias, one_hot=False, wide=False):
     """softmax(x weight^T + bias) per row -- float32 (R, C) -- or, with ``one_hot``, the int64 (R, C) one-hot of each row's
     argmax (the first index on ties), in one launch (cpc_posterior_forward).  x: CUDA fp32 (R, 256) with any row stride;
-    runs on the current stream.  Evaluation only: not differentiable."""
-    _require_cuda(x, "posterior")
-    x, ldx = _rows_of(x, "posterior")
+    runs on the current stream.  Evaluation only: not differentiable.
+    wide: x (R, D) and weight (C, D) with 1 <= D <= 512 (cpc_posterior_forward_d; 256 still goes to the 256 entry point); a
+    width mismatch is a ValueError, a width outside the range NotImplementedError.  Without it any width but 256 is refused."""
+    if wide:
+        x, ldx, D = _rows_of_width(x, weight, "posterior")                   # (a CPU tensor raises there, behind the widths)
+    else:
+        _require_cuda(x, "posterior")
+        x, ldx = _rows_of(x, "posterior")
+        D = _HID
     R, C = x.shape[0], weight.shape[0]
     weight, bias = weight.detach(), bias.detach()
-    if tuple(weight.shape) != (C, _HID) or tuple(bias.shape) != (C,):
-        raise ValueError(f"posterior: weight (C, 256) and bias (C,) expected, got {tuple(weight.shape)} and {tuple(bias.shape)}")
+    if tuple(weight.shape) != (C, D) or tuple(bias.shape) != (C,):
+        raise ValueError(f"posterior: weight (C, {D}) and bias (C,) expected, got {tuple(weight.shape)} and {tuple(bias.shape)}")
     for t in (weight, bias):
         if t.device != x.device or t.dtype != torch.float32:
             raise TypeError("posterior: fp32 parameters on the features' device expected")
     out = torch.empty(R, C, device=x.device, dtype=torch.int64 if one_hot else torch.float32)
     lib = _lib.get()
+    args = (x.data_ptr(), ldx, _p(weight.contiguous()), _p(bias.contiguous()), R, C)
     with torch.cuda.device(x.device):
-        lib.check(lib.cpc_posterior_forward(x.data_ptr(), ldx, _p(weight.contiguous()), _p(bias.contiguous()), R, C,
-                                            1 if one_hot else 0, _p(out), None, _stream()), "posterior_forward")
+        if D == _HID:
+            lib.check(lib.cpc_posterior_forward(*args, 1 if one_hot else 0, _p(out), None, _stream()), "posterior_forward")
+        else:
+            lib.check(lib.cpc_posterior_forward_d(*args, D, 1 if one_hot else 0, _p(out), None, _stream()), "posterior_forward_d")
     return out
 
 

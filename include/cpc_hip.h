@@ -507,6 +507,14 @@ int cpc_phone_head_forward(const float* x, const float* W, const float* b, float
                            int S, int C, void* stream);
 int cpc_phone_head_backward(const float* x, const float* wr, const float* dlogits, float* scratch, float* dW, float* db,
                             float* dX, int B, int S, int C, void* stream);
+/* The head at D input features, Conv1d(D, C, 8, stride 4), 1 <= D <= 512 (CPC_ERR_SHAPE beyond; checked first): x (B, S, D),
+ * W (C, D, 8), wr[o][j * D + c] (C * 8 * D floats), dX (B, S, D); every other limit, order and guarantee as above, and D = 256
+ * gives the bits and the sizes of the calls above.  The CTC calls do not depend on D. */
+int cpc_phone_head_layout_d(int B, int S, int C, int Lmax, int D, long* sizes);
+int cpc_phone_head_forward_d(const float* x, const float* W, const float* b, float* wr, float* scratch, float* logits, int B,
+                             int S, int C, int D, void* stream);
+int cpc_phone_head_backward_d(const float* x, const float* wr, const float* dlogits, float* scratch, float* dW, float* db,
+                              float* dX, int B, int S, int C, int D, void* stream);
 int cpc_ctc_seq_forward(const float* logits, const long long* in_len, const long long* targets, long tgt_stride,
                         const long long* tgt_len, float* saved, float* loss, int B, int T, int C, int Lmax, int blank,
                         int reduction, void* stream);
@@ -533,6 +541,13 @@ int cpc_seqnorm_forward(const float* x, const long long* lengths, const float* s
                         int normalise, void* stream);
 int cpc_seqnorm_backward(const float* x, const float* dy, const long long* lengths, const float* scale, const float* stats,
                          float* dx, int B, int S, int normalise, void* stream);
+/* The same on (B, S, D) features, 1 <= D <= 512 (CPC_ERR_SHAPE beyond; checked first), B * S * D < 2^31: x, y, dy, dx dense at
+ * row pitch D, scale (B, D), stats (B, 2, D).  The 16-byte path also needs D % 4 == 0.  Channel c of an utterance has the same
+ * bits at every D; D = 256 gives the bits of the calls above. */
+int cpc_seqnorm_forward_d(const float* x, const long long* lengths, const float* scale, float* y, float* stats, int B, int S,
+                          int D, int normalise, void* stream);
+int cpc_seqnorm_backward_d(const float* x, const float* dy, const long long* lengths, const float* scale, const float* stats,
+                           float* dx, int B, int S, int D, int normalise, void* stream);
 
 /* ------------------------------------------------------- learned-filter-bank encoder (LFBEnconder) ----
  * cpc/model.py:125-152 (csrc/lfb.hip).  x (N, L) mono waveform, W (2D, 400), b (2D), han (400), all fp32 and read only:
@@ -664,6 +679,13 @@ int cpc_probe_eval_d(const float* x, long ldx, const long long* labels, int R, i
  * of the maximum on ties, as torch.argmax) and 0 elsewhere.  argmax (or NULL): int32 (R), written in both modes. */
 int cpc_posterior_forward(const float* x, long ldx, const float* W, const float* b, int R, int C, int mode, void* out,
                           int* argmax, void* stream);
+/* The same on D features per row, 1 <= D <= 512 (CPC_ERR_SHAPE beyond; checked first): ldx >= D, W (C,D) dense.  LDS rows hold D
+ * rounded up to 16 columns, the padding zero (an MFMA group contracts 16 k; 0 * 0 adds exactly 0).  x and W are read 16 bytes at
+ * a time where D % 4 == 0, the base is 16-byte aligned and (x) ldx % 4 == 0, one float at a time otherwise.  Above 256 features
+ * the class step is 32 and a tile's logits stay in LDS up to 192 classes (64 and 384 otherwise).  D = 256 gives the bits of the
+ * call above. */
+int cpc_posterior_forward_d(const float* x, long ldx, const float* W, const float* b, int R, int C, int D, int mode, void* out,
+                            int* argmax, void* stream);
 
 /* ---------------------------------------------------------------- ABX evaluation ----
  * cpc/eval/ABX.py and cpc/eval/ABX/{abx_group_computation.py, dtw.pyx}: frame distances, normalised DTW and the per-group
