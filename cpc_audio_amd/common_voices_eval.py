@@ -139,10 +139,13 @@ class CTCphone_criterion(torch.nn.Module):
     cpc_seqnorm_*_d); sizeKernel is still 8, and hipHead and hipFront keep their three meanings.  The LSTM is nn.LSTM(dimEncoder,
     dimEncoder): its hidden width follows dimEncoder, and csrc/lstm.hip's recurrence is 256 wide.  So away from 256 the HIP
     front is the HIP seqNorm, then nn.LSTM (MIOpen), then the HIP dropout scale; last_front stays "hip" and last_lstm names the
-    recurrence's path of the last call ("hip", "torch", None without --LSTM or when no front op was active)."""
+    recurrence's path of the last call ("hip", "torch", None without --LSTM or when no front op was active).
+
+    hiddenKernel (off by default; with wideKernel): away from 256 the front's LSTM runs on the LSTM kernels of any hidden width
+    too (ops.LstmHiddenFunction, cpc_lstm_forward_h at D = H = dimEncoder) and last_lstm is "hip" there."""
 
     def __init__(self, dimEncoder, nPhones, LSTM=False, sizeKernel=8, seqNorm=False, dropout=False, reduction='sum',
-                 hipHead=None, hipFront=None, wideKernel=False):
+                 hipHead=None, hipFront=None, wideKernel=False, hiddenKernel=False):
         super().__init__()
         self.hipHead = hipHead
         self.hipFront = hipFront
@@ -158,6 +161,10 @@ class CTCphone_criterion(torch.nn.Module):
             raise NotImplementedError("CTCphone_criterion(hipFront=True): the HIP seqNorm, LSTM and dropout are built for "
                                       f"{widths} (got {dimEncoder})")
         self._hipLstmConfig = dimEncoder == 256            # csrc/lstm.hip: a recurrence 256 wide
+        self.hiddenKernel = bool(hiddenKernel)
+        # ... or, asked for, the recurrence of any hidden width (cpc_lstm_*_h)
+        self._hipLstmHidden = (self.hiddenKernel and self.wideKernel and dimEncoder != 256
+                               and 1 <= dimEncoder <= ops.LSTM_HIDDEN_MAX)
         self.last_path = None
         self.last_front = None
         self.last_lstm = None
@@ -191,7 +198,8 @@ class CTCphone_criterion(torch.nn.Module):
             return False
         B, S, D = cFeature.size()
         ok = cFeature.is_cuda and cFeature.dtype == torch.float32 and ops.seqnorm_supported(B, S, D) and \
-            (not self.useLSTM or not self._hipLstmConfig or ops.lstm_supported(B, S))
+            (not self.useLSTM or not self._hipLstmConfig or ops.lstm_supported(B, S)) and \
+            (not self.useLSTM or not self._hipLstmHidden or ops.lstm_hidden_supported(B, S, 1, D, D))
         if self.hipFront and not ok:
             raise NotImplementedError("CTCphone_criterion(hipFront=True): the HIP front takes CUDA fp32 features of a shape "
                                       f"cpc_seqnorm_forward and cpc_lstm_layout accept (got {tuple(cFeature.size())}, "
@@ -217,7 +225,11 @@ class CTCphone_criterion(torch.nn.Module):
                 self.last_lstm = "hip"
                 cFeature = ops.LstmFunction.apply(cFeature, None, False, self.conv1.weight_ih_l0, self.conv1.weight_hh_l0,
                                                   self.conv1.bias_ih_l0, self.conv1.bias_hh_l0)[0]
-            elif self.useLSTM:                     # a hidden width other than 256: the one piece that stays on MIOpen
+            elif self.useLSTM and self._hipLstmHidden:
+                self.last_lstm = "hip"
+                cFeature = ops.LstmHiddenFunction.apply(cFeature, None, False, self.conv1.weight_ih_l0, self.conv1.weight_hh_l0,
+                                                        self.conv1.bias_ih_l0, self.conv1.bias_hh_l0)[0]
+            elif self.useLSTM:                     # a hidden width other than 256 without hiddenKernel: stays on MIOpen
                 self.last_lstm = "torch"
                 cFeature = self.conv1(cFeature)[0]
             if drop and (self.useLSTM or not self.seqNorm):
@@ -419,6 +431,8 @@ def get_PER_args(args):
     args.hipFront = data.get("hipFront", None)
     if data.get("wideKernel", False):                      # (absent where the training run did not ask for it)
         args.wideKernel = True
+    if data.get("hiddenKernel", False):
+        args.hiddenKernel = True
     return args
 
 
@@ -459,6 +473,9 @@ def parse_args(argv):
     t.add_argument('--wideKernel', action='store_true', default=argparse.SUPPRESS,
                    help="The HIP head and the HIP front at any feature width from 1 to 512 (off by default: 256 only); per reads "
                    "it back from the training run's arguments")
+    t.add_argument('--hiddenKernel', action='store_true', default=argparse.SUPPRESS,
+                   help="With --hipFront --wideKernel --LSTM: the LSTM at a feature width other than 256 on the HIP kernels too "
+                   "(off by default: nn.LSTM there); per reads it back from the training run's arguments")
     p = sub.add_parser('per')
     p.add_argument('output', type=str)
     p.add_argument('--batchSize', type=int, default=8)
@@ -543,7 +560,8 @@ def _main(args):
     feature_maker.cuda()
     phone_criterion = CTCphone_criterion(hidden_gar, n_phones, args.LSTM, seqNorm=args.seqNorm, dropout=args.dropout,
                                          reduction=args.loss_reduction, hipHead=args.hipHead, hipFront=args.hipFront,
-                                         wideKernel=getattr(args, "wideKernel", False)).cuda()
+                                         wideKernel=getattr(args, "wideKernel", False),
+                                         hiddenKernel=getattr(args, "hiddenKernel", False)).cuda()
     print(f"Loading the validation dataset at {args.pathDB}")
     dataset_val = SingleSequenceDataset(args.pathDB, seq_val, phone_labels, inDim=args.in_dim)
     val_loader = DataLoader(dataset_val, batch_size=args.batchSize, shuffle=True)

@@ -1,7 +1,8 @@
 // Host-side code the recurrent cells share (gru.hip, lstm.hip, rnn.hip): what stands around a recurrence kernel is the same for
 // every cell -- the input projection of a layer in front of it, the gradient GEMMs and reductions over all rows behind the
 // backward one, and the choice between one persistent launch and one launch per step.  No device code here: the kernels and the
-// structs they take stay with their cell.  H = kC = 256 is the hidden size of all three.
+// structs they take stay with their cell.  H = kC = 256 is the hidden size of all three; the LSTM at another hidden width
+// (lstm.hip: cpc_lstm_*_h) passes its padded width instead.
 #pragma once
 #include "cpc_common.h"
 #include "cpc_internal.h"
@@ -44,11 +45,12 @@ static int heads_per_launch(K kernel, int block, long wgs_per_head) {
 // (Rec, spin limit) as can be resident together, the launches one after another, over `handover` (the array the steps hand
 // their values over in, `floats` long) pre-filled with the not-ready pattern (persist.h); where not even one head fits, or
 // per_step is set, one launch of `step` (Rec, t) per step for all heads.  head_grid: the workgroups of one head (x, y), 256
-// threads each; the heads ride in blockIdx.z and a launch starts at head Rec::g0.
+// threads each; the heads ride in blockIdx.z and a launch starts at head Rec::g0.  *persistent (if given): which of the two ran.
 template <class Rec, class KP, class KS>
 static int recur_launch(KP persist, KS step, Rec p, dim3 head_grid, int G, int T, bool backward, int per_step, float* handover,
-                        size_t floats, int spin_limit, hipStream_t st) {
+                        size_t floats, int spin_limit, hipStream_t st, bool* persistent = nullptr) {
     const int fit = per_step ? 0 : heads_per_launch(persist, 256, (long)head_grid.x * head_grid.y);
+    if (persistent) *persistent = fit >= 1;
     if (fit >= 1) {
         if (hipMemsetAsync(handover, 0xFF, floats * sizeof(float), st) != hipSuccess) return CPC_ERR_ARG;
         for (p.g0 = 0; p.g0 < G; p.g0 += fit)
@@ -67,11 +69,14 @@ static int recur_launch(KP persist, KS step, Rec p, dim3 head_grid, int G, int T
 // the array's own order: batch-first (sequence r, step t at row r * T + t) or time-major (row t * R + r).
 //   prev_step_rows: row m reads step t - 1 of its sequence -- h_{t-1} -- and a zero row at t = 0
 //   first_step_rows: the R rows at t = 0
-static inline RowMap prev_step_rows(const float* a, int T, int R, long hs, bool time_major) {
+// (a RowMap tells real elements from zeros per 256 columns -- element k at position t * tmul + tadd + (k >> 8) -- so a row of
+// H > 256 columns counts q = ceil(H / 256) positions per step: the whole row of step -1 then lies below position 0)
+static inline RowMap prev_step_rows(const float* a, int T, int R, long hs, bool time_major, int H = kC) {
+    const int q = H > kC ? cdiv(H, kC) : 1;
     RowMap m;
-    m.base = a; m.rstride = (int)hs; m.tmul = 1; m.M = T * R;
-    if (time_major) { m.R = T * R; m.bstride = 0; m.off = -(int)(R * hs); m.tadd = -R; m.Lin = T * R; }
-    else { m.R = T; m.bstride = (long)T * hs; m.off = -(int)hs; m.tadd = -1; m.Lin = T; }
+    m.base = a; m.rstride = (int)hs; m.tmul = q; m.M = T * R;
+    if (time_major) { m.R = T * R; m.bstride = 0; m.off = -(int)(R * hs); m.tadd = -q * R; m.Lin = q * T * R; }
+    else { m.R = T; m.bstride = (long)T * hs; m.off = -(int)hs; m.tadd = -q; m.Lin = q * T; }
     return m;
 }
 static inline RowMap first_step_rows(const float* a, int T, int R, long hs, bool time_major) {
@@ -84,9 +89,9 @@ static inline RowMap first_step_rows(const float* a, int T, int R, long hs, bool
 // Forward input projection of layer l over all M rows: out (M, N) = in . W_ih^T + b_ih, N the gate rows of all heads.  `in` is
 // (M, H), but for layer 0 at an input width D != H, whose product runs in in_proj.hip (ip_scratch: in_proj_w_floats).
 static inline int layer_input_projection(int l, int D, const float* in, const float* wih, const float* bih, float* ip_scratch,
-                                         float* out, int M, int N, hipStream_t st) {
-    return l == 0 && D != kC ? in_proj_forward(in, D, wih, bih, ip_scratch, out, M, N, D, st)
-                             : nt_gemm(plain_rows(in, M, kC), wih, kC, bih, out, N, N, kC, st);
+                                         float* out, int M, int N, hipStream_t st, int H = kC) {
+    return l == 0 && D != H ? in_proj_forward(in, D, wih, bih, ip_scratch, out, M, N, D, st)
+                            : nt_gemm(plain_rows(in, M, H), wih, H, bih, out, N, N, H, st);
 }
 
 // What stands around the backward recurrence of one layer: the weight transposes in front of it (tail_transposes) and,
@@ -104,31 +109,32 @@ struct GradTail {
     float* whhT, *wihT;        // scratch: G * N * H floats each
     float* part, *tmp;         // scratch: the TN GEMMs' split partials, the bias reductions' partial sums
     float* ip_scratch;         // D != H: in_proj_scratch_floats
+    int H = kC;                // hidden width (a multiple of 128: the TN GEMM's tile)
 };
 
 // per head (N,H) -> (H,N); the stacked (G N,H) -> (H,G N), but for a narrow layer 0 (in_proj.hip reads W_ih as it lies)
 static inline int tail_transposes(const GradTail& t, hipStream_t st) {
-    const int rc = transpose(t.w[1], t.whhT, t.N, kC, st, t.G, (long)t.N * kC, (long)t.N * kC);
-    if (rc || t.D != kC) return rc;
-    return transpose(t.w[0], t.wihT, t.G * t.N, kC, st);
+    const int rc = transpose(t.w[1], t.whhT, t.N, t.H, st, t.G, (long)t.N * t.H, (long)t.N * t.H);
+    if (rc || t.D != t.H) return rc;
+    return transpose(t.w[0], t.wihT, t.G * t.N, t.H, st);
 }
 
 // stacked dW_ih = dGi^T . in, dW_hh = dGh^T . h_{t-1} head by head in one launch (+ dGh[t = 0]^T . h0), db_ih = sum dGi,
 // db_hh = sum dGh, dx = dGi . W_ih summed over the heads (as NT against W_ih^T)
 static inline int tail_gradients(const GradTail& t, hipStream_t st) {
-    const int M = t.T * t.R, GN = t.G * t.N;
-    const bool narrow = t.D != kC;
+    const int M = t.T * t.R, GN = t.G * t.N, H = t.H;
+    const bool narrow = t.D != H;
     const RowMap gim = plain_rows(t.dGi, M, GN), ghm = plain_rows(t.dGh, M, GN);
     int rc = narrow ? in_proj_backward(t.in, t.D, t.w[0], t.dGi, t.ip_scratch, nullptr, t.dw[0], M, GN, t.D, st)
-                    : tn_gemm(gim, GN, plain_rows(t.in, M, kC), kC, t.part, t.dw[0], 0, st);
+                    : tn_gemm(gim, GN, plain_rows(t.in, M, H), H, t.part, t.dw[0], 0, st);
     if (rc) return rc;
     GemmGroup grp;
-    grp.G = t.G; grp.a = t.N; grp.b = kC; grp.c = (long)t.N * kC;
-    rc = tn_gemm(ghm, t.N, prev_step_rows(t.out, t.T, t.R, (long)t.G * kC, t.time_major), kC, t.part, t.dw[1], 0, st, GemmBounds(),
+    grp.G = t.G; grp.a = t.N; grp.b = H; grp.c = (long)t.N * H;
+    rc = tn_gemm(ghm, t.N, prev_step_rows(t.out, t.T, t.R, (long)t.G * H, t.time_major, H), H, t.part, t.dw[1], 0, st, GemmBounds(),
                  grp);
     if (rc) return rc;
     if (t.h0) {
-        rc = tn_gemm(first_step_rows(t.dGh, t.T, t.R, GN, t.time_major), t.N, plain_rows(t.h0, t.R, kC), kC, t.part, t.dw[1], 1, st);
+        rc = tn_gemm(first_step_rows(t.dGh, t.T, t.R, GN, t.time_major), t.N, plain_rows(t.h0, t.R, H), H, t.part, t.dw[1], 1, st);
         if (rc) return rc;
     }
     rc = rows_sum(t.dGi, M, GN, t.tmp, t.dw[2], st);
@@ -136,7 +142,7 @@ static inline int tail_gradients(const GradTail& t, hipStream_t st) {
     rc = rows_sum(t.dGh, M, GN, t.tmp, t.dw[3], st);
     if (rc) return rc;
     return narrow ? in_proj_backward(t.in, t.D, t.w[0], t.dGi, t.ip_scratch, t.dx, nullptr, M, GN, t.D, st)
-                  : nt_gemm(gim, t.wihT, GN, nullptr, t.dx, kC, kC, GN, st);
+                  : nt_gemm(gim, t.wihT, GN, nullptr, t.dx, H, H, GN, st);
 }
 
 }  // namespace cpc

@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .ops import EncoderFunction, GruFunction, LstmFunction, RnnFunction
+from .ops import EncoderFunction, GruFunction, LstmFunction, LstmHiddenFunction, RnnFunction
 
 
 class ChannelNorm(nn.Module):
@@ -263,10 +263,14 @@ class CPCAR(nn.Module):
     dimOutput == 256, 1..8 layers: MFCC at 13 / 40 / 80 coefficients, the learned filter bank at 64, CPCEncoder(512) -- to the
     same HIP recurrences for CUDA fp32 input (``self.hip_in``): layer 0's input projection runs at its true width
     (csrc/in_proj.hip, cpc_*_forward_in).  Mode GRU needs nothing else; LSTM and RNN also need their own keyword.  ``self.hip``,
-    ``self.hip_lstm`` and ``self.hip_rnn`` stay False at such a width: they keep meaning the 256 -> 256 kernels."""
+    ``self.hip_lstm`` and ``self.hip_rnn`` stay False at such a width: they keep meaning the 256 -> 256 kernels.
+    ``hiddenKernel=True`` (default off; mode LSTM with ``lstmKernel=True`` only) takes a context width other than 256 --
+    1 <= dimOutput <= 512, any dimEncoded in 1..512, 1..8 layers: --hiddenGar 512 -- to the LSTM kernels of any hidden width
+    for CUDA fp32 input (``self.hip_hidden``; ops.LstmHiddenFunction, cpc_lstm_forward_h).  The four attributes above stay False
+    there.  The GRU and the RNN at another context width keep running baseNet's torch forward."""
 
     def __init__(self, dimEncoded, dimOutput, keepHidden, nLevelsGRU, mode="GRU", reverse=False, lstmKernel=False,
-                 rnnKernel=False, inputKernel=False):
+                 rnnKernel=False, inputKernel=False, hiddenKernel=False):
         super().__init__()
         self.RESIDUAL_STD = 0.1
         self._cell = mode if mode in ("LSTM", "RNN") else "GRU"
@@ -277,6 +281,9 @@ class CPCAR(nn.Module):
         self.hip_lstm = bool(lstmKernel) and mode == "LSTM" and dimEncoded == 256 and dimOutput == 256
         self.hip_rnn = (bool(rnnKernel) and mode == "RNN" and dimEncoded == 256 and dimOutput == 256
                         and 1 <= nLevelsGRU <= 8)
+        self.hip_hidden = (bool(hiddenKernel) and bool(lstmKernel) and mode == "LSTM" and dimOutput != 256
+                           and 1 <= dimOutput <= ops.LSTM_HIDDEN_MAX and 1 <= dimEncoded <= ops.IN_PROJ_MAX
+                           and 1 <= nLevelsGRU <= 8)
         cell = nn.LSTM if mode == "LSTM" else (nn.RNN if mode == "RNN" else nn.GRU)
         self.baseNet = cell(dimEncoded, dimOutput, num_layers=nLevelsGRU, batch_first=True)
         self.hidden = None
@@ -297,8 +304,9 @@ class CPCAR(nn.Module):
         original order (cpc/model.py:185-204); the final hidden state is kept for the next call when keepHidden is set."""
         flip = (lambda t: torch.flip(t, [1])) if self.reverse else (lambda t: t)
         narrow = self.hip_in and x.is_cuda and x.dtype == torch.float32      # (another input width: the same Functions, cpc_*_in)
-        if (self.hip_lstm or narrow and self._cell == "LSTM") and x.is_cuda and x.dtype == torch.float32:
-            y, hN, cN = LstmFunction.apply(flip(x), self.hidden, False, *self._flat_params())
+        if (self.hip_lstm or self.hip_hidden or narrow and self._cell == "LSTM") and x.is_cuda and x.dtype == torch.float32:
+            fn = LstmHiddenFunction if self.hip_hidden else LstmFunction
+            y, hN, cN = fn.apply(flip(x), self.hidden, False, *self._flat_params())
             if self.keepHidden:
                 self.hidden = (hN.detach(), cN.detach())
             out = flip(y)

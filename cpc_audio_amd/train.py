@@ -13,7 +13,7 @@ from .optim import Adam
 
 def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False, reverse=False, arMode="GRU",
                 sizeWindow=20480, abspos=False, transformerDropout=0.1, lstmKernel=False, encoder_type="cpc", rnnKernel=False,
-                mfccKernel=False, inputKernel=False):
+                mfccKernel=False, inputKernel=False, hiddenKernel=False):
     """cpc/feature_loader.py:124-153 (getEncoder / getAR) + cpc/train.py:311.  arMode 'GRU' (north star) or
     'transformer' (BASELINE.json config 4: buildTransformerAR(hiddenEncoder, 1, sizeWindow // 160, abspos)); 'LSTM' /
     'RNN' as the reference (lstmKernel / rnnKernel: the LSTM / the RNN on the HIP kernels, CPCAR); 'no_ar': the identity, and the context width is
@@ -21,7 +21,9 @@ def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False
     mfccKernel=True (not in the reference's signature; default off, as lstmKernel / rnnKernel) builds MFCCEncoder, this package's
     restatement of torchaudio's MFCC on HIP kernels (hiddenEncoder coefficients); without the keyword 'mfcc' raises, since the
     reference's class is torchaudio.transforms.MFCC and torchaudio is not a dependency.  inputKernel=True (default off likewise):
-    a GRU / LSTM / RNN autoregressor behind an encoder of another width than 256 runs the HIP recurrences too (CPCAR)."""
+    a GRU / LSTM / RNN autoregressor behind an encoder of another width than 256 runs the HIP recurrences too (CPCAR).
+    hiddenKernel=True (default off likewise; with arMode 'LSTM' and lstmKernel): a hiddenGar in 1..512 other than 256 runs the
+    LSTM kernels of any hidden width (CPCAR.hip_hidden)."""
     if encoder_type == "mfcc" and not mfccKernel:
         raise NotImplementedError("encoder_type 'mfcc' is torchaudio.transforms.MFCC in the reference; torchaudio is not a "
                                   "dependency of this package.  Pass mfccKernel=True for MFCCEncoder, the package's own "
@@ -39,7 +41,7 @@ def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False
         ar = buildTransformerAR(hiddenEncoder, 1, sizeWindow // 160, abspos, dropout=transformerDropout)
     else:
         ar = CPCAR(hiddenEncoder, hiddenGar, keepHidden, nLevelsGRU, mode=arMode, reverse=reverse, lstmKernel=lstmKernel,
-                   rnnKernel=rnnKernel, inputKernel=inputKernel)
+                   rnnKernel=rnnKernel, inputKernel=inputKernel, hiddenKernel=hiddenKernel)
     return CPCModel(enc, ar)
 
 

@@ -421,6 +421,26 @@ int cpc_rnn_backward_in(const float* x, const float* h0, const float* const* par
                         const float* dy, float* scratch, float* dx, float* const* grads, int T, int R, int nl, int D, int flags,
                         void* stream);
 
+/* ------------------------------------------------------------ the LSTM at any hidden width ----
+ * torch.nn.LSTM(D, H, nl, batch_first=True) with 1 <= D <= 512 and 1 <= H <= 512: x, dx (B,S,D); y, dy (B,S,H); h0, c0 (both or
+ * neither), hN, cN (nl,B,H); params / grads in state-dict order at their TRUE shapes -- weight_ih_l0 (4H,D), weight_ih_l{k>0}
+ * (4H,H), weight_hh (4H,H), biases (4H) -- every gradient fully overwritten.  Inside, the recurrence runs at the padded width
+ * Hp = 128 ceil(H/128) on zero-padded parameter copies (csrc/lstm.hip; a padded unit stays exactly zero), persistent or, for a
+ * grid that cannot be co-resident or with CPC_LSTM_PER_STEP, one launch per step (bit-identical).  `saved` keeps every layer's
+ * padded output, so the backward does not read y (it must still be non-NULL).  A polling time-out raises
+ * CPC_DEVERR_LSTM_POLL_TIMEOUT.  1 <= nl <= 8, B*S <= 2^21 and B*S*4Hp <= 2^31 (so B*S <= 2^20 above H = 384); anything else:
+ * CPC_ERR_SHAPE from all three; a NULL pointer, h0 without c0 or an unknown flag bit: CPC_ERR_ARG; both before any launch.
+ * With H == 256 the *_h entries ARE cpc_lstm_*_in: same launches, same bits, same layout sizes. */
+int cpc_lstm_layout_h(int B, int S, int nl, int D, int H, long* sizes);
+/* Which recurrence kernels the cpc_lstm_forward_h / _backward_h calls of this process (H != 256) have launched since the last
+ * cpc_lstm_paths_h(1): bit 0 a persistent launch, bit 1 per-step launches.  Host-side bookkeeping, no device access. */
+int cpc_lstm_paths_h(int clear);
+int cpc_lstm_forward_h(const float* x, const float* h0, const float* c0, const float* const* params, float* saved, float* scratch,
+                       float* y, float* hN, float* cN, int B, int S, int nl, int D, int H, int flags, void* stream);
+int cpc_lstm_backward_h(const float* x, const float* h0, const float* c0, const float* const* params, const float* saved,
+                        const float* y, const float* dy, float* scratch, float* dx, float* const* grads, int B, int S, int nl,
+                        int D, int H, int flags, void* stream);
+
 /* The projection on its own (csrc/in_proj.hip; exact-f32 MFMAs, so nothing is assumed about the size of x):
  *   cpc_in_proj_forward   out[M,N] = x[M,D] . w[N,D]^T + bias            (bias may be NULL)
  *   cpc_in_proj_backward  dx[M,D] = dg[M,N] . w[N,D]   and   dw[N,D] = dg[M,N]^T . x[M,D]   (both OVERWRITTEN; dx or dw may be
