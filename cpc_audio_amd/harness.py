@@ -491,14 +491,15 @@ def _architecture_args(path):
     return saved
 
 
-def loadModel(pathCheckpoints):
+def loadModel(pathCheckpoints, encoderKernel=False):
     """cpc/feature_loader.py:156-190 for ONE checkpoint: -> (model, hiddenGar, hiddenEncoder).  When the saved arguments carry
     a ``load`` entry that points into another directory (a classifier trained on top of a CPC checkpoint), the architecture is
     read from THAT directory's checkpoint_args.json; the state dict is loaded (strict=False) from the path given.  Arguments
     missing from the file take the reference's defaults (cpc_default_config.py); the autoregressor carries its state from
     call to call when samplingType is "sequential", as getAR builds it.  ``encoder_type`` 'lfb' and ``arMode`` 'no_ar' build LFBEnconder / NoAr
     (hiddenGar is then the encoder's width, cpc/train.py:486); 'mfcc' builds MFCCEncoder (build_model's mfccKernel).  Concatenated models -- more than one checkpoint at
-    either level -- raise ValueError."""
+    either level -- raise ValueError.  encoderKernel=True (default off) is build_model's: a CPCEncoder of another width than 256 on
+    the HIP kernels of any width."""
     from .train import build_model
     if len(pathCheckpoints) != 1:
         raise ValueError("concatenated models (more than one checkpoint) are not supported")
@@ -510,7 +511,8 @@ def loadModel(pathCheckpoints):
     model = build_model(hiddenEncoder=hiddenEncoder, hiddenGar=hiddenGar, nLevelsGRU=saved.get("nLevelsGRU", 1),
                         keepHidden=saved.get("samplingType", "samespeaker") == "sequential",
                         reverse=saved.get("cpc_mode") == "reverse", arMode=arMode, sizeWindow=saved.get("sizeWindow", 20480),
-                        abspos=saved.get("abspos", False), encoder_type=saved.get("encoder_type", "cpc"), mfccKernel=True)
+                        abspos=saved.get("abspos", False), encoder_type=saved.get("encoder_type", "cpc"), mfccKernel=True,
+                        encoderKernel=encoderKernel)
     print(f"Loading the state dict at {path}")
     model.load_state_dict(torch.load(path, map_location="cpu")["gEncoder"], strict=False)
     return model, hiddenGar, hiddenEncoder

@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .ops import EncoderFunction, GruFunction, LstmFunction, LstmHiddenFunction, RnnFunction
+from .ops import EncoderFunction, EncoderWideFunction, GruFunction, LstmFunction, LstmHiddenFunction, RnnFunction
 
 
 class ChannelNorm(nn.Module):
@@ -53,14 +53,21 @@ class CPCEncoder(nn.Module):
     conv{i} / batchNorm{i} carry the reference's names, shapes and default initialisation.  The configuration every BASELINE
     config and the reference's defaults use -- 256 channels, normMode 'layerNorm' (ChannelNorm) -- runs cpc_encoder_forward
     (HIP, ``self.hip``); the reference's other options (``batchNorm`` / ``instanceNorm`` / ``ID``, other widths; cpc/model.py:
-    73-80) are served by the modules' own torch ops: correct on any device, differentiable, not the hot path."""
+    73-80) are served by the modules' own torch ops: correct on any device, differentiable, not the hot path.
 
-    def __init__(self, sizeHidden=512, normMode="layerNorm"):
+    ``encoderKernel=True`` (an addition; default off) takes any other width from 2 to 512 under 'layerNorm' to the encoder kernels
+    of any width for CUDA fp32 input (``self.hip_wide``; ops.EncoderWideFunction, cpc_encoder_forward_c / _backward_c: exact-f32
+    MFMAs on zero-padded storage).  ``self.hip`` keeps meaning the 256 kernels -- what the fused train step tests -- and stays
+    False there; CPU input and other dtypes keep the torch ops.  Parameters, state-dict keys and shapes do not change."""
+
+    def __init__(self, sizeHidden=512, normMode="layerNorm", encoderKernel=False):
         super().__init__()
         validModes = ["batchNorm", "instanceNorm", "ID", "layerNorm"]
         if normMode not in validModes:
             raise ValueError(f"Norm mode must be in {validModes}")
         self.hip = normMode == "layerNorm" and sizeHidden == 256
+        self.hip_wide = (bool(encoderKernel) and normMode == "layerNorm" and sizeHidden != 256
+                         and 2 <= sizeHidden <= ops.ENCODER_WIDE_MAX)
         if normMode == "instanceNorm":
             def normLayer(c): return nn.InstanceNorm1d(c, affine=True)
         elif normMode == "ID":
@@ -96,6 +103,8 @@ class CPCEncoder(nn.Module):
         """(B,1,L) -> (B,C,L/160), as the reference.  The kernels work channels-last, so the
         result is a (B,C,S) VIEW of a contiguous (B,S,C) tensor; CPCModel's permute(0,2,1)
         (model.py:287) therefore yields a contiguous (B,S,C) z at no cost."""
+        if self.hip_wide and x.is_cuda and x.dtype == torch.float32 and self.conv0.weight.dtype == torch.float32:
+            return EncoderWideFunction.apply(x, *self._flat_params()).permute(0, 2, 1)
         if not self.hip:
             for i in range(5):                                 # cpc/model.py:99-105 with the modules' own torch ops
                 x = torch.relu(getattr(self, f"batchNorm{i}")(getattr(self, f"conv{i}")(x)))

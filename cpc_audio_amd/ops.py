@@ -415,6 +415,55 @@ class EncoderFunction(torch.autograd.Function):
         return (None, *grads)
 
 
+ENCODER_WIDE_MAX = 512  # widest CPCEncoder of the encoder kernels of any width (cpc_encoder_*_c; csrc/enc_wide.hip)
+
+
+class EncoderWideFunction(torch.autograd.Function):
+    """wave (B,1,L) + the 20 encoder parameters (state-dict order, C channels, 2 <= C <= 512) -> z (B, L/160, C), contiguous:
+    cpc_encoder_forward_c / _backward_c (csrc/enc_wide.hip; C == 256 runs the 256 kernels behind the same entries).  A plain
+    autograd node on the current stream: no step hooks, no side streams.  The wave receives no gradient."""
+
+    @staticmethod
+    def forward(ctx, wave, *params):
+        _require_cuda(wave, "EncoderWideFunction")
+        lib = _lib.get()
+        B, ch, L = wave.shape
+        if ch != 1 or len(params) != 20:
+            raise ValueError("EncoderWideFunction expects (B,1,L) waveforms and the 20 encoder parameters")
+        C = params[0].shape[0]
+        want = []
+        for i, k in enumerate((10, 8, 4, 4, 4)):
+            want += [(C, 1 if i == 0 else C, k), (C,), (1, C, 1), (1, C, 1)]
+        if not 2 <= C <= ENCODER_WIDE_MAX or [tuple(p.shape) for p in params] != want:
+            raise NotImplementedError(f"cpc_audio_amd.EncoderWideFunction: 2 <= sizeHidden <= {ENCODER_WIDE_MAX} and the "
+                                      f"reference's parameter shapes expected (conv0.weight {tuple(params[0].shape)})")
+        wave = wave.contiguous()
+        params = [p.detach().contiguous() for p in params]
+        with torch.cuda.device(wave.device):
+            sizes = _layout("encoder_layout_c", lib.cpc_encoder_layout_c, 22, B, L, C)
+            saved = torch.empty(sizes[0], device=wave.device, dtype=torch.float32)
+            scratch = torch.empty(max(1, sizes[1]), device=wave.device, dtype=torch.float32)
+            z = torch.empty(B, sizes[7], C, device=wave.device, dtype=torch.float32)
+            lib.check(lib.cpc_encoder_forward_c(_p(wave), _ptrs(params), _p(saved), _p(scratch), _p(z), B, L, C, _stream()),
+                      "encoder_forward_c")
+        ctx.save_for_backward(wave, saved, z, *params)
+        ctx.dims = (B, L, C, sizes[2])
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        lib = _lib.get()
+        wave, saved, z, *params = ctx.saved_tensors
+        B, L, C, nscr = ctx.dims
+        dz = dz.contiguous()
+        with torch.cuda.device(wave.device):
+            scratch = torch.empty(nscr, device=wave.device, dtype=torch.float32)
+            grads = [torch.empty_like(p) for p in params]
+            lib.check(lib.cpc_encoder_backward_c(_p(wave), _ptrs(params), _p(saved), _p(z), _p(dz), _p(scratch), _ptrs(grads),
+                                                 B, L, C, _stream()), "encoder_backward_c")
+        return (None, *grads)
+
+
 IN_PROJ_MAX = 512      # widest layer-0 input of the recurrent cells (cpc_*_in; csrc/in_proj.hip)
 LSTM_HIDDEN_MAX = 512  # widest hidden state of the LSTM at any hidden width (cpc_lstm_*_h; csrc/lstm.hip)
 

@@ -13,7 +13,7 @@ from .optim import Adam
 
 def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False, reverse=False, arMode="GRU",
                 sizeWindow=20480, abspos=False, transformerDropout=0.1, lstmKernel=False, encoder_type="cpc", rnnKernel=False,
-                mfccKernel=False, inputKernel=False, hiddenKernel=False):
+                mfccKernel=False, inputKernel=False, hiddenKernel=False, encoderKernel=False):
     """cpc/feature_loader.py:124-153 (getEncoder / getAR) + cpc/train.py:311.  arMode 'GRU' (north star) or
     'transformer' (BASELINE.json config 4: buildTransformerAR(hiddenEncoder, 1, sizeWindow // 160, abspos)); 'LSTM' /
     'RNN' as the reference (lstmKernel / rnnKernel: the LSTM / the RNN on the HIP kernels, CPCAR); 'no_ar': the identity, and the context width is
@@ -23,7 +23,8 @@ def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False
     reference's class is torchaudio.transforms.MFCC and torchaudio is not a dependency.  inputKernel=True (default off likewise):
     a GRU / LSTM / RNN autoregressor behind an encoder of another width than 256 runs the HIP recurrences too (CPCAR).
     hiddenKernel=True (default off likewise; with arMode 'LSTM' and lstmKernel): a hiddenGar in 1..512 other than 256 runs the
-    LSTM kernels of any hidden width (CPCAR.hip_hidden)."""
+    LSTM kernels of any hidden width (CPCAR.hip_hidden).  encoderKernel=True (default off likewise; encoder_type 'cpc'): a
+    hiddenEncoder in 2..512 other than 256 runs the encoder kernels of any width (CPCEncoder.hip_wide)."""
     if encoder_type == "mfcc" and not mfccKernel:
         raise NotImplementedError("encoder_type 'mfcc' is torchaudio.transforms.MFCC in the reference; torchaudio is not a "
                                   "dependency of this package.  Pass mfccKernel=True for MFCCEncoder, the package's own "
@@ -33,7 +34,8 @@ def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False
     if encoder_type == "mfcc":
         enc = MFCCEncoder(hiddenEncoder)
     else:
-        enc = LFBEnconder(hiddenEncoder) if encoder_type == "lfb" else CPCEncoder(hiddenEncoder, "layerNorm")
+        enc = LFBEnconder(hiddenEncoder) if encoder_type == "lfb" else CPCEncoder(hiddenEncoder, "layerNorm",
+                                                                                             encoderKernel=encoderKernel)
     if arMode == "no_ar":
         ar = NoAr()
     elif arMode == "transformer":

@@ -263,6 +263,22 @@ int cpc_encoder_backward_streams(const float* wave, const float* const* params, 
                                  const float* z, const float* dz, float* scratch, float* const* grads, int B,
                                  int L, void* stream, void* wgrad_stream);
 
+/* The encoder at C channels, 2 <= C <= 512 (csrc/enc_wide.hip): params / grads are the 20 pointers in state-dict order at the
+ * reference's shapes -- conv0.weight (C,1,10), conv{i}.weight (C,C,k), biases (C,), batchNorm{i}.weight / .bias (1,C,1) -- wave
+ * (B,1,L), z and dz (B,L4,C); every gradient is fully overwritten.  cpc_encoder_layout_c fills the same 22 slots as
+ * cpc_encoder_layout; inside `saved` the activations have a row pitch of 64 ceil(C / 64) floats with zero pad columns.
+ * Exact-f32 MFMAs whatever cpc_set_mfma_mode says; no atomics: two calls give the same bits.  C == 256 forwards to the entry
+ * points above (their kernels, layouts and bits).  C < 2 (one channel has no unbiased variance), C > 512 or a shape the index
+ * arithmetic does not cover (B (L + 16) >= 2^30, a window shorter than the five convolutions need): CPC_ERR_SHAPE, checked first and
+ * before any launch; a NULL pointer or a workspace that is not 16-byte aligned: CPC_ERR_ARG. */
+int cpc_encoder_layout_c(int B, int L, int C, long* sizes);
+int cpc_encoder_forward_c(const float* wave, const float* const* params, float* saved, float* scratch, float* z,
+                          int B, int L, int C, void* stream);
+int cpc_encoder_backward_c(const float* wave, const float* const* params, const float* saved, const float* z,
+                           const float* dz, float* scratch, float* const* grads, int B, int L, int C, void* stream);
+/* dst (B,L_layer,C), the true width: the saved output of layer `layer` (0..3) of a cpc_encoder_forward_c.  Tests / debugging. */
+int cpc_encoder_saved_activation_c(const float* saved, int layer, float* dst, int B, int L, int C, void* stream);
+
 /* ------------------------------------------------------------ plain GEMMs ----
  * C[M,N] = A[M,K] . B[N,K]^T + bias[N]   (N % 128 == 0, K % 16 == 0; bias may be NULL).
  * This is torch.nn.Linear's arithmetic (criterion.py:90-91,108; the GRU projections). */
