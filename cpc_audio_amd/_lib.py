@@ -146,6 +146,10 @@ SIGNATURES = {
     "cpc_lstm_paths_h": (_I, [_I]),
     "cpc_lstm_forward_h": (_I, [_P] * 9 + [_I, _I, _I, _I, _I, _I, _P]),
     "cpc_lstm_backward_h": (_I, [_P] * 10 + [_I, _I, _I, _I, _I, _I, _P]),
+    "cpc_gru_layout_h": (_I, [_I, _I, _I, _I, _I, _P]),
+    "cpc_gru_paths_h": (_I, [_I]),
+    "cpc_gru_forward_h": (_I, [_P] * 7 + [_I, _I, _I, _I, _I, _I, _P]),
+    "cpc_gru_backward_h": (_I, [_P] * 9 + [_I, _I, _I, _I, _I, _I, _P]),
     "cpc_rnn_layout_in": (_I, [_I, _I, _I, _I, _P]),
     "cpc_rnn_forward_in": (_I, [_P] * 7 + [_I, _I, _I, _I, _I, _P]),
     "cpc_rnn_backward_in": (_I, [_P] * 9 + [_I, _I, _I, _I, _I, _P]),

@@ -1,8 +1,8 @@
 // Host-side code the recurrent cells share (gru.hip, lstm.hip, rnn.hip): what stands around a recurrence kernel is the same for
 // every cell -- the input projection of a layer in front of it, the gradient GEMMs and reductions over all rows behind the
 // backward one, and the choice between one persistent launch and one launch per step.  No device code here: the kernels and the
-// structs they take stay with their cell.  H = kC = 256 is the hidden size of all three; the LSTM at another hidden width
-// (lstm.hip: cpc_lstm_*_h) passes its padded width instead.
+// structs they take stay with their cell.  H = kC = 256 is the hidden size of all three; the LSTM and the GRU at another hidden
+// width (lstm.hip: cpc_lstm_*_h, gru.hip: cpc_gru_*_h) pass their padded width instead.
 #pragma once
 #include "cpc_common.h"
 #include "cpc_internal.h"

@@ -491,7 +491,7 @@ def _architecture_args(path):
     return saved
 
 
-def loadModel(pathCheckpoints, encoderKernel=False):
+def loadModel(pathCheckpoints, encoderKernel=False, hiddenKernel=False):
     """cpc/feature_loader.py:156-190 for ONE checkpoint: -> (model, hiddenGar, hiddenEncoder).  When the saved arguments carry
     a ``load`` entry that points into another directory (a classifier trained on top of a CPC checkpoint), the architecture is
     read from THAT directory's checkpoint_args.json; the state dict is loaded (strict=False) from the path given.  Arguments
@@ -499,7 +499,9 @@ def loadModel(pathCheckpoints, encoderKernel=False):
     call to call when samplingType is "sequential", as getAR builds it.  ``encoder_type`` 'lfb' and ``arMode`` 'no_ar' build LFBEnconder / NoAr
     (hiddenGar is then the encoder's width, cpc/train.py:486); 'mfcc' builds MFCCEncoder (build_model's mfccKernel).  Concatenated models -- more than one checkpoint at
     either level -- raise ValueError.  encoderKernel=True (default off) is build_model's: a CPCEncoder of another width than 256 on
-    the HIP kernels of any width."""
+    the HIP kernels of any width.  hiddenKernel=True (default off) is build_model's too: a GRU checkpoint trained at another
+    hiddenGar than 256 opens on the GRU kernels of any hidden width (an LSTM checkpoint also needs lstmKernel, which this
+    function does not take: it stays on torch)."""
     from .train import build_model
     if len(pathCheckpoints) != 1:
         raise ValueError("concatenated models (more than one checkpoint) are not supported")
@@ -512,7 +514,7 @@ def loadModel(pathCheckpoints, encoderKernel=False):
                         keepHidden=saved.get("samplingType", "samespeaker") == "sequential",
                         reverse=saved.get("cpc_mode") == "reverse", arMode=arMode, sizeWindow=saved.get("sizeWindow", 20480),
                         abspos=saved.get("abspos", False), encoder_type=saved.get("encoder_type", "cpc"), mfccKernel=True,
-                        encoderKernel=encoderKernel)
+                        encoderKernel=encoderKernel, hiddenKernel=hiddenKernel)
     print(f"Loading the state dict at {path}")
     model.load_state_dict(torch.load(path, map_location="cpu")["gEncoder"], strict=False)
     return model, hiddenGar, hiddenEncoder

@@ -10,7 +10,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .ops import EncoderFunction, EncoderWideFunction, GruFunction, LstmFunction, LstmHiddenFunction, RnnFunction
+from .ops import (EncoderFunction, EncoderWideFunction, GruFunction, GruHiddenFunction, LstmFunction, LstmHiddenFunction,
+                  RnnFunction)
 
 
 class ChannelNorm(nn.Module):
@@ -273,10 +274,13 @@ class CPCAR(nn.Module):
     same HIP recurrences for CUDA fp32 input (``self.hip_in``): layer 0's input projection runs at its true width
     (csrc/in_proj.hip, cpc_*_forward_in).  Mode GRU needs nothing else; LSTM and RNN also need their own keyword.  ``self.hip``,
     ``self.hip_lstm`` and ``self.hip_rnn`` stay False at such a width: they keep meaning the 256 -> 256 kernels.
-    ``hiddenKernel=True`` (default off; mode LSTM with ``lstmKernel=True`` only) takes a context width other than 256 --
-    1 <= dimOutput <= 512, any dimEncoded in 1..512, 1..8 layers: --hiddenGar 512 -- to the LSTM kernels of any hidden width
-    for CUDA fp32 input (``self.hip_hidden``; ops.LstmHiddenFunction, cpc_lstm_forward_h).  The four attributes above stay False
-    there.  The GRU and the RNN at another context width keep running baseNet's torch forward."""
+    ``hiddenKernel=True`` (default off) takes a context width other than 256 -- 1 <= dimOutput <= 512, any dimEncoded in
+    1..512, 1..8 layers: --hiddenGar 512 -- to the kernels of any hidden width for CUDA fp32 input.  Mode LSTM (with
+    ``lstmKernel=True``, as above) runs ops.LstmHiddenFunction (cpc_lstm_forward_h; ``self.hip_hidden``, which keeps meaning the
+    LSTM kernels).  Mode GRU needs nothing else -- ``inputKernel``'s rule -- and runs ops.GruHiddenFunction (cpc_gru_forward_h;
+    ``self.hip_gru_hidden``); that is the one combination whose path the keyword changes for a GRU: (GRU, ``hiddenKernel=True``,
+    dimOutput != 256) leaves nn.GRU's torch forward for the HIP recurrence.  The four attributes above stay False in both cases.
+    The RNN at another context width keeps running baseNet's torch forward."""
 
     def __init__(self, dimEncoded, dimOutput, keepHidden, nLevelsGRU, mode="GRU", reverse=False, lstmKernel=False,
                  rnnKernel=False, inputKernel=False, hiddenKernel=False):
@@ -293,6 +297,9 @@ class CPCAR(nn.Module):
         self.hip_hidden = (bool(hiddenKernel) and bool(lstmKernel) and mode == "LSTM" and dimOutput != 256
                            and 1 <= dimOutput <= ops.LSTM_HIDDEN_MAX and 1 <= dimEncoded <= ops.IN_PROJ_MAX
                            and 1 <= nLevelsGRU <= 8)
+        self.hip_gru_hidden = (bool(hiddenKernel) and self._cell == "GRU" and dimOutput != 256
+                               and 1 <= dimOutput <= ops.GRU_HIDDEN_MAX and 1 <= dimEncoded <= ops.IN_PROJ_MAX
+                               and 1 <= nLevelsGRU <= 8)
         cell = nn.LSTM if mode == "LSTM" else (nn.RNN if mode == "RNN" else nn.GRU)
         self.baseNet = cell(dimEncoded, dimOutput, num_layers=nLevelsGRU, batch_first=True)
         self.hidden = None
@@ -329,6 +336,16 @@ class CPCAR(nn.Module):
                 self.hidden = hN.detach()
             out = flip(y)
             out._cpc_abs_bound = 1.0                           # |tanh| <= 1 whatever h0 is
+            return out
+        if self.hip_gru_hidden and x.is_cuda and x.dtype == torch.float32:
+            # the 256 GRU's rule below: |h_t| <= 1 from zero or from the module's own last state only
+            bounded = self.hidden is None or self.hidden is getattr(self, "_own_hidden", None)
+            y, h_last = GruHiddenFunction.apply(flip(x), self.hidden, False, *self._flat_params())
+            if self.keepHidden:
+                self.hidden = self._own_hidden = h_last.detach()
+            out = flip(y)
+            if bounded:
+                out._cpc_abs_bound = 1.0
             return out
         if not (self.hip or narrow):                           # cpc/model.py:185-204 with baseNet's own torch forward
             y, h = self.baseNet(flip(x), self.hidden)

@@ -739,6 +739,83 @@ def lstm_hidden_supported(B, S, nl, D, H):
     return True
 
 
+GRU_HIDDEN_MAX = 512   # widest hidden state of the GRU at any hidden width (cpc_gru_*_h; csrc/gru.hip)
+
+
+class GruHiddenFunction(torch.autograd.Function):
+    """nn.GRU(D, H, nl, batch_first=True) at any hidden width: x (B,S,D), h0 None or (nl,B,H), 4*nl GRU parameters at their true
+    shapes -> y (B,S,H), hN (nl,B,H), 1 <= D, H <= 512 (cpc_gru_forward_h / _backward_h: the recurrence runs at the padded width
+    128 * ceil(H / 128) on zero-padded weight copies; with H == 256 the entries are cpc_gru_*_in, which take no per_step).  A plain
+    Function -- one stream, no prepared coefficients: the carried state gets no gradient, hN is not differentiable, per_step
+    selects the one-launch-per-step kernels (same bits)."""
+
+    @staticmethod
+    def forward(ctx, x, h0, per_step, *params):
+        _require_cuda(x, "GruHiddenFunction")
+        lib = _lib.get()
+        nl = len(params) // 4
+        if x.dim() != 3 or nl < 1 or len(params) != 4 * nl or params[1].dim() != 2 or params[0].dim() != 2:
+            raise NotImplementedError("cpc_audio_amd.GruHiddenFunction: x (B,S,D) and 4 parameters per nn.GRU layer expected")
+        B, S, D = x.shape
+        H = params[1].shape[1]
+        shapes = []
+        for l in range(nl):
+            shapes += [(3 * H, D if l == 0 else H), (3 * H, H), (3 * H,), (3 * H,)]
+        if [tuple(p.shape) for p in params] != shapes or x.dtype != torch.float32:
+            raise NotImplementedError(f"cpc_audio_amd.GruHiddenFunction: fp32 nn.GRU({D}, {H}, {nl}) parameters expected, got "
+                                      f"{[tuple(p.shape) for p in params]}")
+        x = x.contiguous()
+        params = [p.detach().contiguous() for p in params]
+        h0 = None if h0 is None else h0.detach().contiguous()
+        if h0 is not None and tuple(h0.shape) != (nl, B, H):
+            raise NotImplementedError(f"cpc_audio_amd.GruHiddenFunction: carried state of shape {(nl, B, H)} expected")
+        flags = 1 if per_step else 0                      # CPC_GRU_PER_STEP
+        with torch.cuda.device(x.device):
+            sizes = _layout("gru_layout_h", lib.cpc_gru_layout_h, 3, B, S, nl, D, H)
+            saved = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
+            scratch = torch.empty(sizes[1], device=x.device, dtype=torch.float32)
+            y = torch.empty(B, S, H, device=x.device, dtype=torch.float32)
+            hN = torch.empty(nl, B, H, device=x.device, dtype=torch.float32)
+            lib.check(lib.cpc_gru_forward_h(_p(x), _p(h0), _ptrs(params), _p(saved), _p(scratch), _p(y), _p(hN), B, S, nl, D, H,
+                                            flags, _stream()), "gru_forward_h")
+        ctx.save_for_backward(x, saved, y, *params)
+        ctx.h0 = h0
+        ctx.dims = (B, S, nl, D, H, sizes[2], flags)
+        ctx.mark_non_differentiable(hN)
+        ctx.set_materialize_grads(False)
+        return y, hN
+
+    @staticmethod
+    def backward(ctx, dy, _dhN):
+        lib = _lib.get()
+        x, saved, y, *params = ctx.saved_tensors
+        B, S, nl, D, H, nscr, flags = ctx.dims
+        dy = torch.zeros_like(y) if dy is None else dy.contiguous()
+        with torch.cuda.device(x.device):
+            scratch = torch.empty(nscr, device=x.device, dtype=torch.float32)
+            dx = torch.empty_like(x)
+            grads = [torch.empty_like(p) for p in params]
+            lib.check(lib.cpc_gru_backward_h(_p(x), _p(ctx.h0), _ptrs(params), _p(saved), _p(y), _p(dy), _p(scratch), _p(dx),
+                                             _ptrs(grads), B, S, nl, D, H, flags, _stream()), "gru_backward_h")
+        return (dx, None, None, *grads)
+
+
+def gru_hidden_paths(clear=True):
+    """Which recurrence kernels GruHiddenFunction has launched since the last clearing call: a set out of "persistent" and
+    "per_step" (cpc_gru_paths_h; per_step is the residency fallback of a grid that cannot be co-resident, or the flag)."""
+    mask = _lib.get().cpc_gru_paths_h(1 if clear else 0)
+    return {name for bit, name in ((1, "persistent"), (2, "per_step")) if mask & bit}
+
+
+def gru_hidden_supported(B, S, nl, D, H):
+    """Does cpc_gru_layout_h take nn.GRU(D, H, nl) on (B, S, D)?"""
+    try:
+        _layout("gru_layout_h", _lib.get().cpc_gru_layout_h, 3, int(B), int(S), int(nl), int(D), int(H))
+    except ValueError:
+        return False
+    return True
+
+
 def lstm_supported(B, S, nl=1):
     """Does cpc_lstm_layout take nl layers on (B, S, 256)?"""
     try:

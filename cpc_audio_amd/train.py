@@ -22,8 +22,9 @@ def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False
     restatement of torchaudio's MFCC on HIP kernels (hiddenEncoder coefficients); without the keyword 'mfcc' raises, since the
     reference's class is torchaudio.transforms.MFCC and torchaudio is not a dependency.  inputKernel=True (default off likewise):
     a GRU / LSTM / RNN autoregressor behind an encoder of another width than 256 runs the HIP recurrences too (CPCAR).
-    hiddenKernel=True (default off likewise; with arMode 'LSTM' and lstmKernel): a hiddenGar in 1..512 other than 256 runs the
-    LSTM kernels of any hidden width (CPCAR.hip_hidden).  encoderKernel=True (default off likewise; encoder_type 'cpc'): a
+    hiddenKernel=True (default off likewise): a hiddenGar in 1..512 other than 256 runs the recurrence kernels of any hidden
+    width -- arMode 'GRU' with nothing else (CPCAR.hip_gru_hidden), arMode 'LSTM' with lstmKernel (CPCAR.hip_hidden); the RNN at
+    such a width stays on torch.  encoderKernel=True (default off likewise; encoder_type 'cpc'): a
     hiddenEncoder in 2..512 other than 256 runs the encoder kernels of any width (CPCEncoder.hip_wide)."""
     if encoder_type == "mfcc" and not mfccKernel:
         raise NotImplementedError("encoder_type 'mfcc' is torchaudio.transforms.MFCC in the reference; torchaudio is not a "

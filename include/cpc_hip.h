@@ -457,6 +457,32 @@ int cpc_lstm_backward_h(const float* x, const float* h0, const float* c0, const 
                         const float* y, const float* dy, float* scratch, float* dx, float* const* grads, int B, int S, int nl,
                         int D, int H, int flags, void* stream);
 
+/* ------------------------------------------------------------ the GRU at any hidden width ----
+ * torch.nn.GRU(D, H, nl, batch_first=True) with 1 <= D <= 512, 1 <= H <= 512 and 1 <= nl <= 8: x, dx (B,S,D); y, dy (B,S,H);
+ * h0 (or NULL), hN (nl,B,H); params / grads in state-dict order at their TRUE shapes -- weight_ih_l0 (3H,D), weight_ih_l{k>0}
+ * (3H,H), weight_hh (3H,H), biases (3H) -- every gradient fully overwritten; the carried state gets no gradient.  Inside, the
+ * recurrence runs at the padded width Hp = 128 ceil(H/128) on zero-padded parameter copies (csrc/gru.hip).  A padded unit has
+ * r = z = 1/2 and n = 0, so h' = h_prev / 2: it stays exactly zero because the carried h0 is padded with WRITTEN zeros.  One
+ * persistent launch per layer and direction or, for a grid that cannot be co-resident or with CPC_GRU_PER_STEP, one launch
+ * per step (bit-identical); exact-f32 MFMAs, no atomics on floats.  `saved` keeps every layer's padded output, so the backward
+ * does not read y (it must still be non-NULL).  A polling time-out raises CPC_DEVERR_GRU_POLL_TIMEOUT and the budget is
+ * cpc_set_gru_spin_limit's.
+ * Shapes: the GEMM row maps index B*S rows with 21 bits, and row offsets into the (B,S,3Hp) arrays are 32-bit: B*S <= 2^21 and
+ * B*S*3Hp <= 2^31 (the second binds above H = 256: B*S <= 1864135 at Hp = 384, <= 1398101 at Hp = 512).  Anything else:
+ * CPC_ERR_SHAPE from all three; a NULL pointer or an unknown flag bit: CPC_ERR_ARG; both before any launch.
+ * With H == 256 the *_h entries ARE cpc_gru_*_in: same launches, same bits, same layout sizes; CPC_GRU_PER_STEP is refused there
+ * with CPC_ERR_ARG (that path's choice belongs to cpc_set_gru_mode). */
+#define CPC_GRU_PER_STEP 1
+int cpc_gru_layout_h(int B, int S, int nl, int D, int H, long* sizes);      /* sizes[0..2]: saved / forward / backward scratch */
+/* Which recurrence kernels the cpc_gru_forward_h / _backward_h calls of this process (H != 256) have launched since the last
+ * cpc_gru_paths_h(1): bit 0 a persistent launch, bit 1 per-step launches.  Host-side bookkeeping, no device access. */
+int cpc_gru_paths_h(int clear);
+int cpc_gru_forward_h(const float* x, const float* h0, const float* const* params, float* saved, float* scratch, float* y,
+                      float* hN, int B, int S, int nl, int D, int H, int flags, void* stream);
+int cpc_gru_backward_h(const float* x, const float* h0, const float* const* params, const float* saved, const float* y,
+                       const float* dy, float* scratch, float* dx, float* const* grads, int B, int S, int nl, int D, int H,
+                       int flags, void* stream);
+
 /* The projection on its own (csrc/in_proj.hip; exact-f32 MFMAs, so nothing is assumed about the size of x):
  *   cpc_in_proj_forward   out[M,N] = x[M,D] . w[N,D]^T + bias            (bias may be NULL)
  *   cpc_in_proj_backward  dx[M,D] = dg[M,N] . w[N,D]   and   dw[N,D] = dg[M,N]^T . x[M,D]   (both OVERWRITTEN; dx or dw may be
