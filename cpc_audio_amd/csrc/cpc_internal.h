@@ -90,6 +90,9 @@ int tn_gemm_batch(int nprob, const RowMap* am, int N1, const RowMap* bm, int N2,
 int transpose(const float* in, float* out, int R, int Cn, hipStream_t st, int G = 1, long in_gs = 0, long out_gs = 0);
 // n <= 4 matrices of one shape in one launch
 int transpose_batch(const float* const* in, float* const* out, int n, int R, int Cn, hipStream_t st);
+// dst (ng, dr, dc) from src (ng, sr, sc): the common part copied, the rest of dst WRITTEN zeros.  Pads parameters, carried state
+// and dy of the cells at any hidden width to the padded width and narrows outputs and gradients back (padded_cell.h)
+int pad_copy(const float* src, float* dst, int ng, long sr, int sc, long dr, int dc, hipStream_t st);
 
 // ---- in_proj.hip: layer 0's input projection of the recurrent cells at an input width D in 1..kInProjMaxD other than 256
 // (exact-f32 MFMAs; x and dx rows ldx >= D floats apart, any 4-byte alignment; N % 128 == 0; out, dG and scratch 16-byte aligned)

@@ -292,6 +292,17 @@ __global__ __launch_bounds__(256) void transpose_batch_kernel(TransposeBatch b, 
     }
 }
 
+// dst (ng, dr, dc) from src (ng, sr, sc): the common part copied, the rest of dst zero (any alignment: scalar accesses)
+__global__ __launch_bounds__(256) void pad_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, int ng, long sr,
+                                                       int sc, long dr, int dc) {
+    const long n = (long)ng * dr * dc;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < n; idx += (long)gridDim.x * 256) {
+        const int c = (int)(idx % dc);
+        const long gr = idx / dc, r = gr % dr, g = gr / dr;
+        dst[idx] = r < sr && c < sc ? src[(g * sr + r) * sc + c] : 0.f;
+    }
+}
+
 // One workgroup of 1024 threads per (array, slot): slot s covers elements [s, s+1) * ceil(n / 64 / 4) * 4 of its array,
 // four 16-byte loads in flight per thread.
 // (a job without an array -- x == NULL -- is a bound known a priori: its slots all carry cval)
@@ -584,11 +595,19 @@ int transpose_batch(const float* const* in, float* const* out, int n, int R, int
     return 0;
 }
 
+int pad_copy(const float* src, float* dst, int ng, long sr, int sc, long dr, int dc, hipStream_t st) {
+    const long n = (long)ng * dr * dc, blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(pad_copy_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, src, dst, ng, sr, sc,
+                       dr, dc);
+    CPC_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace cpc
 
 using namespace cpc;
 
-// C[M,N] = A[M,K] . B[N,K]^T + bias   (lda/ldb/ldc in floats; bias may be NULL)
+// C[M,N] = A[M,K] . B[N,K]^T + bias  (lda/ldb/ldc in floats; bias may be NULL)
 extern "C" int cpc_gemm_nt(const float* A, int lda, const float* B, int ldb, const float* bias, float* C,
                            int ldc, int M, int N, int K, void* stream) {
     CPC_RETURN_IF(!A || !B || !C, CPC_ERR_ARG);

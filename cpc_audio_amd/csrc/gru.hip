@@ -30,6 +30,7 @@
 #include "gemm_tile.h"
 #include "persist.h"
 #include "recurrent_host.h"
+#include "padded_cell.h"
 
 namespace cpc {
 
@@ -1736,13 +1737,13 @@ static int gru_backward_impl(const float* x, const float* h0, const float* const
 
 // ================================================================== any hidden width H in 1..512 (cpc_gru_*_h)
 // The same recurrence at a padded width Hp = 128 * ceil(H / 128) on zero-padded copies of the parameters, made once per layer
-// and call in scratch (the scheme of lstm.hip's cpc_lstm_*_h).  Every internal (B,S,.) array is Hp or 3 Hp floats wide, gate g
+// and call in scratch (padded_cell.h: the scheme, shared with lstm.hip's cpc_lstm_*_h).  Every internal (B,S,.) array is Hp or 3 Hp floats wide, gate g
 // of unit j at column g * Hp + j; y, hN, dx and the gradients are narrowed to their true shapes by a copy at the end.
 // Why a padded unit stays exactly zero -- the GRU's own argument, not the LSTM's:
 //   * forward: zero W_ih and W_hh rows and zero biases give r = z = sigmoid(0) = 1/2 and n = tanh(0 + 1/2 * 0) = 0, so
 //     h' = 1/2 * 0 + 1/2 * h_prev.  The unit stays 0 ONLY IF ITS h0 IS 0: unlike the LSTM's o * tanh(c), the GRU's output mixes
 //     the previous state in, and a padded h0 left as scratch would decay as 2^-t through y.  The carried h0 is therefore padded
-//     with WRITTEN zeros (gruh_copy) in the forward and in the backward; without a carried state the kernels start from 0.f.
+//     with WRITTEN zeros (pad_copy, by padded_cell.h's drivers) in the forward and in the backward; without a carried state the kernels start from 0.f.
 //     Its zero W_hh column keeps it out of every real unit's product whatever it holds -- as long as it is finite, which 0 is.
 //   * backward: a padded unit's dh is 0 (dy's padding) + dh_{t+1} * 1/2 + (dGh_{t+1} . a zero column of W_hh) = 0 by induction
 //     from dh_S = 0, so dar = daz = dan = 0 exactly and its dGi / dGh columns are written zeros, which meet zero weights only.
@@ -1755,6 +1756,9 @@ static int gru_backward_impl(const float* x, const float* h0, const float* const
 //     stay at 48 registers beside the 12 KF of W_hh^T.
 //   * exact-f32 MFMAs throughout, so nothing is assumed about the size of h0.
 //   * the tail products are recurrent_host.h's at N = 3 Hp, H = Hp: layer 0 at D != Hp in in_proj.hip, the rest on nt_gemm / tn_gemm.
+// What does not depend on the cell is padded_cell.h's: the kernels' index prologue (PadTile), operand loads and products, the
+// layout, the width dispatch and the forward / backward drivers.  Here: the records, the gate math, the kernels and the cell's
+// description for the drivers (GruHCell).
 namespace cpc {
 
 struct GruHFwd {
@@ -1782,45 +1786,6 @@ struct GruHBwd {
     int g0;
 };
 
-// dst (ng, dr, dc) from src (ng, sr, sc): the common part copied, the rest of dst zero.  Pads parameters, the carried state and
-// dy to the padded width and narrows outputs and gradients back (any alignment: scalar accesses).
-__global__ __launch_bounds__(256) void gruh_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, int ng, long sr,
-                                                        int sc, long dr, int dc) {
-    const long n = (long)ng * dr * dc;
-    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < n; idx += (long)gridDim.x * 256) {
-        const int c = (int)(idx % dc);
-        const long gr = idx / dc, r = gr % dr, g = gr / dr;
-        dst[idx] = r < sr && c < sc ? src[(g * sr + r) * sc + c] : 0.f;
-    }
-}
-
-// Lane (i, kq) of wave w holds W_hh[gate * Hp + j0 + i][koff + 16 ii .. + 4], koff = 16 KF w + 4 kq
-template <int KF>
-__device__ __forceinline__ void gruh_load_whh(float4 (&bw)[3][KF], const float* __restrict__ whh, int j0, int i, int koff) {
-    constexpr int HP = 64 * KF;
-#pragma unroll
-    for (int g = 0; g < 3; ++g)
-#pragma unroll
-        for (int ii = 0; ii < KF; ++ii)
-            bw[g][ii] = *reinterpret_cast<const float4*>(whh + (long)(g * HP + j0 + i) * HP + koff + 16 * ii);
-}
-
-template <int KF>
-__device__ __forceinline__ void gruh_fwd_mfma(float (&part)[4][3][256], const float4 (&a)[KF], const float4 (&bw)[3][KF], int w,
-                                              int i, int kq) {
-#pragma unroll
-    for (int g = 0; g < 3; ++g) {
-        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ii = 0; ii < KF; ++ii)
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(f4c(a[ii], jj), f4c(bw[g][ii], jj), acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) part[w][g][(kq * 4 + r) * 16 + i] = acc[r];
-    }
-}
-
 // gru_step_fwd_kernel's gate math at width HP; hp: h_{t-1} of this (b, j)
 template <int HP>
 __device__ __forceinline__ float gruh_fwd_gates(const float (&part)[4][3][256], int tid, const GruHFwd& p, long bt, int j,
@@ -1841,45 +1806,32 @@ __device__ __forceinline__ float gruh_fwd_gates(const float (&part)[4][3][256], 
     return h;
 }
 
-template <int KF>
-__device__ __forceinline__ void gruh_load_h(float4 (&a)[KF], const GruHFwd& p, int b, bool ok, int koff, int t) {
-    constexpr int HP = 64 * KF;
-    const float* src = t == 0 ? (p.h0 ? p.h0 + (long)b * HP : nullptr) : p.y + ((long)b * p.S + t - 1) * HP;
-#pragma unroll
-    for (int ii = 0; ii < KF; ++ii)
-        a[ii] = ok && src ? *reinterpret_cast<const float4*>(src + koff + 16 * ii) : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
 // grid = (Hp/16, ceil(B/16)), 256 threads; every workgroup resident at once (recur_launch).  The workgroup's W_hh slice
 // (3 KF float4 per lane) stays in registers for all S steps, and the gate thread of (b, j) keeps the h_{t-1} it produced itself.
 template <int KF>
 __global__ __launch_bounds__(256) void gruh_persist_fwd_kernel(GruHFwd p, int spin_limit) {
     constexpr int HP = 64 * KF;
     __shared__ float part[4][3][256];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int i = lane & 15, kq = lane >> 4;
-    const int j0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
-    const int koff = 16 * KF * w + 4 * kq;
+    PadTile q;
+    const int koff = 16 * KF * q.w + 4 * q.kq;
     float4 bw[3][KF];
-    gruh_load_whh<KF>(bw, p.whh, j0, i, koff);
-    const bool ok = (b0 + i) < p.B;
-    const int arow = ok ? b0 + i : b0;
-    const int b = b0 + (tid >> 4), j = j0 + (tid & 15);
-    const bool live = b < p.B;
-    float hp = live && p.h0 ? p.h0[(long)b * HP + j] : 0.f;
+    pad_load_whh<3, KF>(bw, p.whh, q.j0, q.i, koff);
+    q.feed_row(p.B);
+    q.gate_thread(p.B);
+    float hp = q.live && p.h0 ? p.h0[(long)q.b * HP + q.j] : 0.f;
     int budget = spin_limit;
     PollPace pace(-1);
     for (int t = 0; t < p.S; ++t) {
         float4 a[KF];
-        if (t == 0) gruh_load_h<KF>(a, p, arow, ok, koff, 0);
-        else poll_frags<KF, 16>(p.y + ((long)arow * p.S + t - 1) * HP + koff, ok, a, budget, pace, &g_gru_poll_timeout);
-        gruh_fwd_mfma<KF>(part, a, bw, w, i, kq);
+        if (t == 0) pad_load_h<KF>(a, p.h0, p.y, p.S, q.arow, q.ok, koff, 0);
+        else poll_frags<KF, 16>(p.y + ((long)q.arow * p.S + t - 1) * HP + koff, q.ok, a, budget, pace, &g_gru_poll_timeout);
+        pad_fwd_mfma<3, KF>(part, a, bw, q.w, q.i, q.kq);
         __syncthreads();
-        if (live) {
-            const long bt = (long)b * p.S + t;
-            hp = gruh_fwd_gates<HP>(part, tid, p, bt, j, hp);
-            store_coherent(p.y + bt * HP + j, hp);
-            if (t == p.S - 1) p.hN[(long)b * HP + j] = hp;
+        if (q.live) {
+            const long bt = (long)q.b * p.S + t;
+            hp = gruh_fwd_gates<HP>(part, q.tid, p, bt, q.j, hp);
+            store_coherent(p.y + bt * HP + q.j, hp);
+            if (t == p.S - 1) p.hN[(long)q.b * HP + q.j] = hp;
         }
         __syncthreads();
     }
@@ -1890,47 +1842,23 @@ template <int KF>
 __global__ __launch_bounds__(256) void gruh_step_fwd_kernel(GruHFwd p, int t) {
     constexpr int HP = 64 * KF;
     __shared__ float part[4][3][256];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int i = lane & 15, kq = lane >> 4;
-    const int j0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
-    const int koff = 16 * KF * w + 4 * kq;
+    PadTile q;
+    const int koff = 16 * KF * q.w + 4 * q.kq;
     float4 bw[3][KF];
-    gruh_load_whh<KF>(bw, p.whh, j0, i, koff);
-    const bool ok = (b0 + i) < p.B;
+    pad_load_whh<3, KF>(bw, p.whh, q.j0, q.i, koff);
+    q.feed_row(p.B);
     float4 a[KF];
-    gruh_load_h<KF>(a, p, ok ? b0 + i : b0, ok, koff, t);
-    gruh_fwd_mfma<KF>(part, a, bw, w, i, kq);
+    pad_load_h<KF>(a, p.h0, p.y, p.S, q.arow, q.ok, koff, t);
+    pad_fwd_mfma<3, KF>(part, a, bw, q.w, q.i, q.kq);
     __syncthreads();
-    const int b = b0 + (tid >> 4), j = j0 + (tid & 15);
-    if (b >= p.B) return;
+    q.gate_thread(p.B);
+    if (!q.live) return;
+    const int b = q.b, j = q.j;
     const long bt = (long)b * p.S + t;
     const float hp = t > 0 ? p.y[(bt - 1) * HP + j] : (p.h0 ? p.h0[(long)b * HP + j] : 0.f);
-    const float h = gruh_fwd_gates<HP>(part, tid, p, bt, j, hp);
+    const float h = gruh_fwd_gates<HP>(part, q.tid, p, bt, j, hp);
     p.y[bt * HP + j] = h;
     if (t == p.S - 1) p.hN[(long)b * HP + j] = h;
-}
-
-// ---- backward: K = 3 Hp, a wave's quarter is 3 Hp / 4 = 16 * (3 KF) wide
-template <int KF> struct GruHB {
-    static constexpr int HP = 64 * KF, GP = 3 * HP, NF = 3 * KF;        // NF fragments per lane (6, 12, 18, 24) ...
-    static constexpr int CH = NF <= 16 ? NF : NF / 2, NCH = NF / CH;    // ... fetched and multiplied CH (6, 12, 9, 12) at a time
-};
-
-template <int KF>
-__device__ __forceinline__ void gruh_load_whhT(float4 (&bw)[3 * KF], const float* __restrict__ whhT, int j0, int i, int koff) {
-#pragma unroll
-    for (int ii = 0; ii < 3 * KF; ++ii)
-        bw[ii] = *reinterpret_cast<const float4*>(whhT + (long)(j0 + i) * (192 * KF) + koff + 16 * ii);
-}
-
-// one piece of the contraction: fragments c0 .. c0 + CH of this lane
-template <int KF, int CH>
-__device__ __forceinline__ void gruh_bwd_piece(f32x4& acc, const float4 (&a)[CH], const float4 (&bw)[3 * KF], int c0) {
-#pragma unroll
-    for (int ii = 0; ii < CH; ++ii)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(f4c(a[ii], jj), f4c(bw[c0 + ii], jj), acc, 0, 0, 0);
 }
 
 // gru_step_bwd_kernel's gate math at width HP.  dh in: dh_{t+1} (unread at t == S - 1), out: dh_t; zn: z_{t+1}.
@@ -1956,40 +1884,36 @@ __device__ __forceinline__ float gruh_bwd_gates(const float (&part)[4][256], int
 
 template <int KF>
 __global__ __launch_bounds__(256) void gruh_persist_bwd_kernel(GruHBwd p, int spin_limit) {
-    using W = GruHB<KF>;
+    using W = PadBwd<3, KF>;
     constexpr int HP = W::HP, GP = W::GP, CH = W::CH;
     __shared__ float part[4][256];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int i = lane & 15, kq = lane >> 4;
-    const int j0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
-    const int koff = (GP / 4) * w + 4 * kq;
+    PadTile q;
+    const int koff = GP / 4 * q.w + 4 * q.kq;
     float4 bw[W::NF];
-    gruh_load_whhT<KF>(bw, p.whhT, j0, i, koff);
-    const bool ok = (b0 + i) < p.B;
-    const int arow = ok ? b0 + i : b0;
-    const int b = b0 + (tid >> 4), j = j0 + (tid & 15);
-    const bool live = b < p.B;
+    pad_load_whhT<3, KF>(bw, p.whhT, q.j0, q.i, koff);
+    q.feed_row(p.B);
+    q.gate_thread(p.B);
     float dh = 0.f, zn = 0.f;                        // dh_{t+1} and z_{t+1} of this (b, j): produced / read here one step ago
     int budget = spin_limit;
     PollPace pace(-1), nopace(0);                    // (the later pieces of a step follow the first at once)
     for (int t = p.S - 1; t >= 0; --t) {
         f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
         if (t < p.S - 1) {                           // (t == S - 1: dGh_{t+1} = 0, the product is 0)
-            const float* row = p.dGh + ((long)arow * p.S + t + 1) * GP + koff;
+            const float* row = p.dGh + ((long)q.arow * p.S + t + 1) * GP + koff;
 #pragma unroll
-            for (int q = 0; q < W::NCH; ++q) {
+            for (int c = 0; c < W::NCH; ++c) {
                 float4 a[CH];
-                poll_frags<CH, 16>(row + 16 * CH * q, ok, a, budget, q == 0 ? pace : nopace, &g_gru_poll_timeout);
-                gruh_bwd_piece<KF, CH>(acc, a, bw, CH * q);
+                poll_frags<CH, 16>(row + 16 * CH * c, q.ok, a, budget, c == 0 ? pace : nopace, &g_gru_poll_timeout);
+                pad_bwd_piece<W::NF, CH>(acc, a, bw, CH * c);
             }
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) part[w][(kq * 4 + r) * 16 + i] = acc[r];
+        for (int r = 0; r < 4; ++r) part[q.w][(q.kq * 4 + r) * 16 + q.i] = acc[r];
         __syncthreads();
-        if (live) {
+        if (q.live) {
             float dg[4];
-            zn = gruh_bwd_gates<HP>(part, tid, p, b, j, t, dh, zn, dg);
-            const long o = ((long)b * p.S + t) * GP + j;
+            zn = gruh_bwd_gates<HP>(part, q.tid, p, q.b, q.j, t, dh, zn, dg);
+            const long o = ((long)q.b * p.S + t) * GP + q.j;
             store_coherent(p.dGh + o, dg[0]);
             store_coherent(p.dGh + o + HP, dg[1]);
             store_coherent(p.dGh + o + 2 * HP, dg[3]);
@@ -2001,33 +1925,32 @@ __global__ __launch_bounds__(256) void gruh_persist_bwd_kernel(GruHBwd p, int sp
 
 template <int KF>
 __global__ __launch_bounds__(256) void gruh_step_bwd_kernel(GruHBwd p, int t) {
-    using W = GruHB<KF>;
+    using W = PadBwd<3, KF>;
     constexpr int HP = W::HP, GP = W::GP, CH = W::CH;
     __shared__ float part[4][256];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int i = lane & 15, kq = lane >> 4;
-    const int j0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
-    const int koff = (GP / 4) * w + 4 * kq;
+    PadTile q;
+    const int koff = GP / 4 * q.w + 4 * q.kq;
     float4 bw[W::NF];
-    gruh_load_whhT<KF>(bw, p.whhT, j0, i, koff);
-    const bool ok = (b0 + i) < p.B;
+    pad_load_whhT<3, KF>(bw, p.whhT, q.j0, q.i, koff);
+    q.feed_row(p.B);
     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
     if (t + 1 < p.S) {
-        const float* row = p.dGh + ((long)(ok ? b0 + i : b0) * p.S + t + 1) * GP + koff;
+        const float* row = p.dGh + ((long)q.arow * p.S + t + 1) * GP + koff;
 #pragma unroll
-        for (int q = 0; q < W::NCH; ++q) {
+        for (int c = 0; c < W::NCH; ++c) {
             float4 a[CH];
 #pragma unroll
             for (int ii = 0; ii < CH; ++ii)
-                a[ii] = ok ? *reinterpret_cast<const float4*>(row + 16 * (CH * q + ii)) : make_float4(0.f, 0.f, 0.f, 0.f);
-            gruh_bwd_piece<KF, CH>(acc, a, bw, CH * q);
+                a[ii] = q.ok ? *reinterpret_cast<const float4*>(row + 16 * (CH * c + ii)) : make_float4(0.f, 0.f, 0.f, 0.f);
+            pad_bwd_piece<W::NF, CH>(acc, a, bw, CH * c);
         }
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) part[w][(kq * 4 + r) * 16 + i] = acc[r];
+    for (int r = 0; r < 4; ++r) part[q.w][(q.kq * 4 + r) * 16 + q.i] = acc[r];
     __syncthreads();
-    const int b = b0 + (tid >> 4), j = j0 + (tid & 15);
-    if (b >= p.B) return;
+    q.gate_thread(p.B);
+    if (!q.live) return;
+    const int b = q.b, j = q.j;
     const long bt = (long)b * p.S + t;
     float dh = 0.f, zn = 0.f;
     if (t + 1 < p.S) {
@@ -2035,7 +1958,7 @@ __global__ __launch_bounds__(256) void gruh_step_bwd_kernel(GruHBwd p, int t) {
         zn = p.Z[(bt + 1) * HP + j];
     }
     float dg[4];
-    gruh_bwd_gates<HP>(part, tid, p, b, j, t, dh, zn, dg);
+    gruh_bwd_gates<HP>(part, q.tid, p, b, j, t, dh, zn, dg);
     const long o = bt * GP + j;
     p.dGh[o] = dg[0]; p.dGh[o + HP] = dg[1]; p.dGh[o + 2 * HP] = dg[3];
     p.dGi[o] = dg[0]; p.dGi[o + HP] = dg[1]; p.dGi[o + 2 * HP] = dg[2];
@@ -2043,182 +1966,37 @@ __global__ __launch_bounds__(256) void gruh_step_bwd_kernel(GruHBwd p, int t) {
 }
 
 // ------------------------------------------------------------------ host side
-static inline int gruh_padded(int H) { return 128 * cdiv(H, 128); }
-
-struct GruHLayout {
-    int Hp;
-    long R[8], Z[8], N[8], GHN[8], Y[8];                      // saved: every layer keeps its padded output
-    long saved_total;
-    long gx, wih, whh, bih, bhh, h0, hN, ipf, fwd_total;
-    long whhT, wihT, wihp, whhp, dGi, dGh, DH, mid[2], bh0, gwih, gwhh, gbih, gbhh, part, tmp, ipb, bwd_total;
-};
-
-// The limits: the GEMM row maps (gemm_tile.h) count B * S rows in 21 bits, and a row offset into a (B,S,3Hp) array is 32-bit.
-static bool gruh_layout(int B, int S, int nl, int D, int H, GruHLayout& g) {
-    if (B <= 0 || S <= 0 || nl <= 0 || nl > 8 || D < 1 || D > kInProjMaxD || H < 1 || H > 512) return false;
-    const int Hp = gruh_padded(H), Gp = 3 * Hp;
-    const long M = (long)B * S;
-    if (M > (1L << 21) || M * Gp > (1L << 31)) return false;
-    g.Hp = Hp;
-    const long mh = align64l(M * Hp), mg = align64l(M * Gp), wi = (long)Gp * (D > Hp ? D : Hp), wh = (long)Gp * Hp;
-    const long st = align64l((long)nl * B * Hp), bh = align64l((long)B * Hp);
-    long o = 0;
-    for (int l = 0; l < nl; ++l) {
-        g.R[l] = o; o += mh;
-        g.Z[l] = o; o += mh;
-        g.N[l] = o; o += mh;
-        g.GHN[l] = o; o += mh;
-        g.Y[l] = o; o += mh;
-    }
-    g.saved_total = o;
-    o = 0;
-    g.gx = o; o += mg;
-    g.wih = o; o += align64l(wi);
-    g.whh = o; o += wh;
-    g.bih = o; o += Gp;
-    g.bhh = o; o += Gp;
-    g.h0 = o; o += st;
-    g.hN = o; o += st;
-    g.ipf = o; o += in_proj_w_floats(Gp, D);
-    g.fwd_total = o;
-    o = 0;
-    g.whhT = o; o += wh;
-    g.wihT = o; o += wh;
-    g.wihp = o; o += align64l(wi);
-    g.whhp = o; o += wh;
-    g.dGi = o; o += mg;
-    g.dGh = o; o += mg;
-    g.DH = o; o += bh;
-    g.mid[0] = o; o += mh;
-    g.mid[1] = o; o += mh;
-    g.bh0 = o; o += bh;
-    g.gwih = o; o += align64l(wi);
-    g.gwhh = o; o += wh;
-    g.gbih = o; o += Gp;
-    g.gbhh = o; o += Gp;
-    g.part = o; o += align64l(tn_gemm_part_floats((int)M, Gp, Hp));
-    g.tmp = o; o += align64l((long)kRowsSumGroups * Gp);
-    g.ipb = o; o += in_proj_scratch_floats(M, Gp, D);
-    g.bwd_total = o;
-    return true;
-}
-
-static int gruh_copy(const float* src, float* dst, int ng, long sr, int sc, long dr, int dc, hipStream_t st) {
-    const long n = (long)ng * dr * dc, blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(gruh_copy_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, src, dst, ng, sr, sc,
-                       dr, dc);
-    CPC_LAUNCH_CHECK();
-    return 0;
-}
-
-// Which recurrence kernels the cpc_gru_*_h calls of this process launched since the last cpc_gru_paths_h(1):
-// bit 0 a persistent one, bit 1 the per-step ones (the residency fallback of recur_launch, or CPC_GRU_PER_STEP).
+// Which recurrence kernels the cpc_gru_*_h calls of this process launched since the last cpc_gru_paths_h(1)
 static int g_gruh_paths = 0;
 
-template <int KF>
-static int gruh_recur_kf(const GruHFwd& p, int per_step, hipStream_t st) {
-    bool persistent = false;
-    const int rc = recur_launch(gruh_persist_fwd_kernel<KF>, gruh_step_fwd_kernel<KF>, p, dim3(4 * KF, cdiv(p.B, 16)), 1, p.S,
-                                false, per_step, p.y, (size_t)p.B * p.S * 64 * KF, g_gru_spin_limit, st, &persistent);
-    g_gruh_paths |= persistent ? 1 : 2;
-    return rc;
-}
-template <int KF>
-static int gruh_recur_kf(const GruHBwd& p, int per_step, hipStream_t st) {
-    bool persistent = false;
-    const int rc = recur_launch(gruh_persist_bwd_kernel<KF>, gruh_step_bwd_kernel<KF>, p, dim3(4 * KF, cdiv(p.B, 16)), 1, p.S,
-                                true, per_step, p.dGh, (size_t)p.B * p.S * 192 * KF, g_gru_spin_limit, st, &persistent);
-    g_gruh_paths |= persistent ? 1 : 2;
-    return rc;
-}
-// the instantiation of the padded width Hp in {128, 256, 384, 512}
-template <class Rec>
-static int gruh_recur(const Rec& p, int Hp, int per_step, hipStream_t st) {
-    switch (Hp) {
-        case 128: return gruh_recur_kf<2>(p, per_step, st);
-        case 256: return gruh_recur_kf<4>(p, per_step, st);
-        case 384: return gruh_recur_kf<6>(p, per_step, st);
-        case 512: return gruh_recur_kf<8>(p, per_step, st);
+// The cell as padded_cell.h's layout and drivers see it.  Saved per layer: R, Z, N, GHN, Y (B,S,Hp); carried: h0, padded with
+// written zeros by the drivers (see the top); the backward's own: dGi, dGh (B,S,3Hp; dGh is polled), DH (B,Hp).
+struct GruHCell {
+    static constexpr int NG = 3, NS = 1, kDGh = 1, kPerStep = CPC_GRU_PER_STEP;
+    static constexpr const char* kSaved = "hhhhh";
+    static constexpr const char* kOwn = "ggs";
+    using Fwd = GruHFwd;
+    using Bwd = GruHBwd;
+    static void fill(Fwd& p, float* saved, const long* slot, const float* const* s0, float* const* sN) {
+        p.R = saved + slot[0]; p.Z = saved + slot[1]; p.N = saved + slot[2]; p.GHN = saved + slot[3];
+        p.h0 = s0[0]; p.hN = sN[0];
     }
-    return CPC_ERR_SHAPE;
-}
-
-#define GRUH_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
-
-static int gruh_forward(const float* x, const float* h0, const float* const* params, float* saved, float* scratch, float* y,
-                        float* hN, int B, int S, int nl, int D, int H, int flags, void* stream) {
-    GruHLayout g;
-    CPC_RETURN_IF(!gruh_layout(B, S, nl, D, H, g), CPC_ERR_SHAPE);
-    CPC_RETURN_IF(flags & ~CPC_GRU_PER_STEP, CPC_ERR_ARG);
-    CPC_RETURN_IF(!x || !ptrs_ok(params, 4 * nl) || !saved || !scratch || !y || !hN, CPC_ERR_ARG);
-    hipStream_t st = (hipStream_t)stream;
-    const int Hp = g.Hp, Gp = 3 * Hp, M = B * S;
-    if (h0) GRUH_TRY(gruh_copy(h0, scratch + g.h0, 1, (long)nl * B, H, (long)nl * B, Hp, st));      // (written zeros: see the top)
-    const float* in = x;
-    for (int l = 0; l < nl; ++l) {
-        const int Dl = l == 0 ? D : H, Dlp = l == 0 ? D : Hp;          // true and internal width of this layer's input
-        GRUH_TRY(gruh_copy(params[4 * l], scratch + g.wih, 3, H, Dl, Hp, Dlp, st));
-        GRUH_TRY(gruh_copy(params[4 * l + 1], scratch + g.whh, 3, H, H, Hp, Hp, st));
-        GRUH_TRY(gruh_copy(params[4 * l + 2], scratch + g.bih, 3, 1, H, 1, Hp, st));
-        GRUH_TRY(gruh_copy(params[4 * l + 3], scratch + g.bhh, 3, 1, H, 1, Hp, st));
-        GRUH_TRY(layer_input_projection(l, D, in, scratch + g.wih, scratch + g.bih, scratch + g.ipf, scratch + g.gx, M, Gp, st, Hp));
-        GruHFwd p;
-        p.gx = scratch + g.gx; p.whh = scratch + g.whh; p.bhh = scratch + g.bhh;
-        p.h0 = h0 ? scratch + g.h0 + (long)l * B * Hp : nullptr;
-        p.y = saved + g.Y[l]; p.R = saved + g.R[l]; p.Z = saved + g.Z[l]; p.N = saved + g.N[l]; p.GHN = saved + g.GHN[l];
-        p.hN = scratch + g.hN + (long)l * B * Hp;
-        p.B = B; p.S = S; p.g0 = 0;
-        GRUH_TRY(gruh_recur(p, Hp, flags & CPC_GRU_PER_STEP, st));
-        in = p.y;
+    static void fill(Bwd& p, const float* saved, const long* slot, const float* const* s0, float* scratch, const long* own) {
+        p.R = saved + slot[0]; p.Z = saved + slot[1]; p.N = saved + slot[2]; p.GHN = saved + slot[3]; p.y = saved + slot[4];
+        p.h0 = s0[0];
+        p.dGi = scratch + own[0]; p.dGh = scratch + own[1]; p.DH = scratch + own[2];
     }
-    GRUH_TRY(gruh_copy(in, y, 1, M, Hp, M, H, st));
-    return gruh_copy(scratch + g.hN, hN, 1, (long)nl * B, Hp, (long)nl * B, H, st);
-}
-
-static int gruh_backward(const float* x, const float* h0, const float* const* params, const float* saved, const float* y,
-                         const float* dy, float* scratch, float* dx, float* const* grads, int B, int S, int nl, int D, int H,
-                         int flags, void* stream) {
-    GruHLayout g;
-    CPC_RETURN_IF(!gruh_layout(B, S, nl, D, H, g), CPC_ERR_SHAPE);
-    CPC_RETURN_IF(flags & ~CPC_GRU_PER_STEP, CPC_ERR_ARG);
-    CPC_RETURN_IF(!x || !ptrs_ok(params, 4 * nl) || !saved || !y || !dy || !scratch || !dx ||
-                  !ptrs_ok(const_cast<const float* const*>(grads), 4 * nl), CPC_ERR_ARG);
-    hipStream_t st = (hipStream_t)stream;
-    const int Hp = g.Hp, Gp = 3 * Hp, M = B * S;
-    // dy at the padded width in the mid[] slot the top layer does not write (the layer below it may: dy is spent by then)
-    float* dyp = scratch + g.mid[nl & 1];
-    GRUH_TRY(gruh_copy(dy, dyp, 1, M, H, M, Hp, st));
-    const float* dYl = dyp;
-    for (int l = nl - 1; l >= 0; --l) {
-        const int Dl = l == 0 ? D : H, Dlp = l == 0 ? D : Hp;
-        GRUH_TRY(gruh_copy(params[4 * l], scratch + g.wihp, 3, H, Dl, Hp, Dlp, st));
-        GRUH_TRY(gruh_copy(params[4 * l + 1], scratch + g.whhp, 3, H, H, Hp, Hp, st));
-        if (h0) GRUH_TRY(gruh_copy(h0 + (long)l * B * H, scratch + g.bh0, 1, B, H, B, Hp, st));
-        const float* wp[4] = {scratch + g.wihp, scratch + g.whhp, nullptr, nullptr};      // (the tail reads no bias)
-        float* gp[4] = {scratch + g.gwih, scratch + g.gwhh, scratch + g.gbih, scratch + g.gbhh};
-        GradTail t;
-        t.H = Hp; t.N = Gp; t.G = 1; t.T = S; t.R = B; t.D = Dlp; t.time_major = false;
-        t.dGi = scratch + g.dGi; t.dGh = scratch + g.dGh;
-        t.in = l == 0 ? x : saved + g.Y[l - 1]; t.out = saved + g.Y[l];
-        t.h0 = h0 ? scratch + g.bh0 : nullptr;
-        t.w = wp; t.dw = gp; t.dx = l == 0 ? dx : scratch + g.mid[l & 1];
-        t.whhT = scratch + g.whhT; t.wihT = scratch + g.wihT; t.part = scratch + g.part; t.tmp = scratch + g.tmp;
-        t.ip_scratch = scratch + g.ipb;
-        GRUH_TRY(tail_transposes(t, st));
-        GruHBwd p;
-        p.whhT = t.whhT; p.dY = dYl; p.y = t.out; p.h0 = t.h0;
-        p.R = saved + g.R[l]; p.Z = saved + g.Z[l]; p.N = saved + g.N[l]; p.GHN = saved + g.GHN[l];
-        p.dGi = scratch + g.dGi; p.dGh = scratch + g.dGh; p.DH = scratch + g.DH; p.B = B; p.S = S; p.g0 = 0;
-        GRUH_TRY(gruh_recur(p, Hp, flags & CPC_GRU_PER_STEP, st));
-        GRUH_TRY(tail_gradients(t, st));
-        GRUH_TRY(gruh_copy(gp[0], grads[4 * l], 3, Hp, Dlp, H, Dl, st));
-        GRUH_TRY(gruh_copy(gp[1], grads[4 * l + 1], 3, Hp, Hp, H, H, st));
-        GRUH_TRY(gruh_copy(gp[2], grads[4 * l + 2], 3, 1, Hp, 1, H, st));
-        GRUH_TRY(gruh_copy(gp[3], grads[4 * l + 3], 3, 1, Hp, 1, H, st));
-        dYl = t.dx;
+    template <int KF>
+    static int recur(const Fwd& p, int per_step, hipStream_t st) {
+        return padded_recur_kf(gruh_persist_fwd_kernel<KF>, gruh_step_fwd_kernel<KF>, p, KF, false, p.y, 1, g_gru_spin_limit,
+                               per_step, &g_gruh_paths, st);
     }
-    return 0;
-}
+    template <int KF>
+    static int recur(const Bwd& p, int per_step, hipStream_t st) {
+        return padded_recur_kf(gruh_persist_bwd_kernel<KF>, gruh_step_bwd_kernel<KF>, p, KF, true, p.dGh, NG, g_gru_spin_limit,
+                               per_step, &g_gruh_paths, st);
+    }
+};
 
 }  // namespace cpc
 
@@ -2231,8 +2009,8 @@ extern "C" int cpc_gru_paths_h(int clear) {
 
 extern "C" int cpc_gru_layout_h(int B, int S, int nl, int D, int H, long* sizes) {
     if (H == kH) return cpc_gru_layout_in(B, S, nl, D, sizes);
-    GruHLayout g;
-    return layout_sizes(gruh_layout(B, S, nl, D, H, g), g, sizes);
+    PaddedLayout g;
+    return layout_sizes(padded_layout<GruHCell>(B, S, nl, D, H, g), g, sizes);
 }
 
 extern "C" int cpc_gru_forward_h(const float* x, const float* h0, const float* const* params, float* saved, float* scratch, float* y,
@@ -2241,7 +2019,7 @@ extern "C" int cpc_gru_forward_h(const float* x, const float* h0, const float* c
         CPC_RETURN_IF(flags != 0, CPC_ERR_ARG);
         return cpc_gru_forward_in(x, h0, params, saved, scratch, y, hN, B, S, nl, D, stream);
     }
-    return gruh_forward(x, h0, params, saved, scratch, y, hN, B, S, nl, D, H, flags, stream);
+    return padded_forward<GruHCell>(x, &h0, params, saved, scratch, y, &hN, B, S, nl, D, H, flags, stream);
 }
 
 extern "C" int cpc_gru_backward_h(const float* x, const float* h0, const float* const* params, const float* saved, const float* y,
@@ -2251,7 +2029,7 @@ extern "C" int cpc_gru_backward_h(const float* x, const float* h0, const float* 
         CPC_RETURN_IF(flags != 0, CPC_ERR_ARG);
         return cpc_gru_backward_in(x, h0, params, saved, y, dy, scratch, dx, grads, B, S, nl, D, stream);
     }
-    return gruh_backward(x, h0, params, saved, y, dy, scratch, dx, grads, B, S, nl, D, H, flags, stream);
+    return padded_backward<GruHCell>(x, &h0, params, saved, y, dy, scratch, dx, grads, B, S, nl, D, H, flags, stream);
 }
 
 #ifdef CPC_GRU_TIMING

@@ -32,6 +32,7 @@
 #include "gemm_tile.h"
 #include "persist.h"
 #include "recurrent_host.h"
+#include "padded_cell.h"
 
 namespace cpc {
 
@@ -497,6 +498,9 @@ extern "C" int cpc_lstm_group_backward(const float* x, const float* w_ih, const 
 //   * the backward polls its 4 KF fragments in pieces of at most 16 and multiplies each piece before it fetches the next: the
 //     MFMA order is that of one pass, the live fragments stay at 64 registers beside the 16 KF of W_hh^T.
 //   * the tail products are recurrent_host.h's at H = Hp: layer 0 at D != Hp in in_proj.hip, everything else on nt_gemm / tn_gemm.
+// What does not depend on the cell is padded_cell.h's, shared with gru.hip: the kernels' index prologue (PadTile), operand loads
+// and products, the layout, the width dispatch and the forward / backward drivers.  Here: the records, the gate math, the
+// kernels and the cell's description for the drivers (LstmHCell).
 namespace cpc {
 
 struct LstmHFwd {
@@ -526,45 +530,6 @@ struct LstmHBwd {
     int g0;
 };
 
-// dst (ng, dr, dc) from src (ng, sr, sc): the common part copied, the rest of dst zero.  Pads parameters, carried state and dy to
-// the padded width and narrows outputs and gradients back (any alignment: scalar accesses).
-__global__ __launch_bounds__(256) void lstmh_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, int ng, long sr,
-                                                         int sc, long dr, int dc) {
-    const long n = (long)ng * dr * dc;
-    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < n; idx += (long)gridDim.x * 256) {
-        const int c = (int)(idx % dc);
-        const long gr = idx / dc, r = gr % dr, g = gr / dr;
-        dst[idx] = r < sr && c < sc ? src[(g * sr + r) * sc + c] : 0.f;
-    }
-}
-
-// Lane (i, kq) of wave w holds W_hh[gate * Hp + j0 + i][koff + 16 ii .. + 4], koff = 16 KF w + 4 kq
-template <int KF>
-__device__ __forceinline__ void lstmh_load_whh(float4 (&bw)[4][KF], const float* __restrict__ whh, int j0, int i, int koff) {
-    constexpr int HP = 64 * KF;
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int ii = 0; ii < KF; ++ii)
-            bw[g][ii] = *reinterpret_cast<const float4*>(whh + (long)(g * HP + j0 + i) * HP + koff + 16 * ii);
-}
-
-template <int KF>
-__device__ __forceinline__ void lstmh_fwd_mfma(float (&part)[4][4][256], const float4 (&a)[KF], const float4 (&bw)[4][KF], int w,
-                                               int i, int kq) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ii = 0; ii < KF; ++ii)
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(f4c(a[ii], jj), f4c(bw[g][ii], jj), acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) part[w][g][(kq * 4 + r) * 16 + i] = acc[r];
-    }
-}
-
 template <int HP>
 __device__ __forceinline__ float lstmh_fwd_gates(const float (&part)[4][4][256], int tid, const LstmHFwd& p, long bt, int j,
                                                  float& c) {
@@ -582,46 +547,33 @@ __device__ __forceinline__ float lstmh_fwd_gates(const float (&part)[4][4][256],
     return h;
 }
 
-template <int KF>
-__device__ __forceinline__ void lstmh_load_h(float4 (&a)[KF], const LstmHFwd& p, int b, bool ok, int koff, int t) {
-    constexpr int HP = 64 * KF;
-    const float* src = t == 0 ? (p.h0 ? p.h0 + (long)b * HP : nullptr) : p.y + ((long)b * p.S + t - 1) * HP;
-#pragma unroll
-    for (int ii = 0; ii < KF; ++ii)
-        a[ii] = ok && src ? *reinterpret_cast<const float4*>(src + koff + 16 * ii) : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
 // grid = (Hp/16, ceil(B/16)), 256 threads; every workgroup resident at once (recur_launch)
 template <int KF>
 __global__ __launch_bounds__(256) void lstmh_persist_fwd_kernel(LstmHFwd p, int spin_limit) {
     constexpr int HP = 64 * KF;
     __shared__ float part[4][4][256];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int i = lane & 15, kq = lane >> 4;
-    const int j0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
-    const int koff = 16 * KF * w + 4 * kq;
+    PadTile q;
+    const int koff = 16 * KF * q.w + 4 * q.kq;
     float4 bw[4][KF];
-    lstmh_load_whh<KF>(bw, p.whh, j0, i, koff);
-    const bool ok = (b0 + i) < p.B;
-    const int arow = ok ? b0 + i : b0;
-    const int b = b0 + (tid >> 4), j = j0 + (tid & 15);
-    const bool live = b < p.B;
-    float c = live && p.c0 ? p.c0[(long)b * HP + j] : 0.f;
+    pad_load_whh<4, KF>(bw, p.whh, q.j0, q.i, koff);
+    q.feed_row(p.B);
+    q.gate_thread(p.B);
+    float c = q.live && p.c0 ? p.c0[(long)q.b * HP + q.j] : 0.f;
     int budget = spin_limit;
     PollPace pace(-1);
     for (int t = 0; t < p.S; ++t) {
         float4 a[KF];
-        if (t == 0) lstmh_load_h<KF>(a, p, arow, ok, koff, 0);
-        else poll_frags<KF, 16>(p.y + ((long)arow * p.S + t - 1) * HP + koff, ok, a, budget, pace, &g_lstm_poll_timeout);
-        lstmh_fwd_mfma<KF>(part, a, bw, w, i, kq);
+        if (t == 0) pad_load_h<KF>(a, p.h0, p.y, p.S, q.arow, q.ok, koff, 0);
+        else poll_frags<KF, 16>(p.y + ((long)q.arow * p.S + t - 1) * HP + koff, q.ok, a, budget, pace, &g_lstm_poll_timeout);
+        pad_fwd_mfma<4, KF>(part, a, bw, q.w, q.i, q.kq);
         __syncthreads();
-        if (live) {
-            const long bt = (long)b * p.S + t;
-            const float h = lstmh_fwd_gates<HP>(part, tid, p, bt, j, c);
-            store_coherent(p.y + bt * HP + j, h);
+        if (q.live) {
+            const long bt = (long)q.b * p.S + t;
+            const float h = lstmh_fwd_gates<HP>(part, q.tid, p, bt, q.j, c);
+            store_coherent(p.y + bt * HP + q.j, h);
             if (t == p.S - 1) {
-                p.hN[(long)b * HP + j] = h;
-                p.cN[(long)b * HP + j] = c;
+                p.hN[(long)q.b * HP + q.j] = h;
+                p.cN[(long)q.b * HP + q.j] = c;
             }
         }
         __syncthreads();
@@ -632,50 +584,26 @@ template <int KF>
 __global__ __launch_bounds__(256) void lstmh_step_fwd_kernel(LstmHFwd p, int t) {
     constexpr int HP = 64 * KF;
     __shared__ float part[4][4][256];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int i = lane & 15, kq = lane >> 4;
-    const int j0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
-    const int koff = 16 * KF * w + 4 * kq;
+    PadTile q;
+    const int koff = 16 * KF * q.w + 4 * q.kq;
     float4 bw[4][KF];
-    lstmh_load_whh<KF>(bw, p.whh, j0, i, koff);
-    const bool ok = (b0 + i) < p.B;
+    pad_load_whh<4, KF>(bw, p.whh, q.j0, q.i, koff);
+    q.feed_row(p.B);
     float4 a[KF];
-    lstmh_load_h<KF>(a, p, ok ? b0 + i : b0, ok, koff, t);
-    lstmh_fwd_mfma<KF>(part, a, bw, w, i, kq);
+    pad_load_h<KF>(a, p.h0, p.y, p.S, q.arow, q.ok, koff, t);
+    pad_fwd_mfma<4, KF>(part, a, bw, q.w, q.i, q.kq);
     __syncthreads();
-    const int b = b0 + (tid >> 4), j = j0 + (tid & 15);
-    if (b >= p.B) return;
+    q.gate_thread(p.B);
+    if (!q.live) return;
+    const int b = q.b, j = q.j;
     const long bt = (long)b * p.S + t;
     float c = t > 0 ? p.C[(bt - 1) * HP + j] : (p.c0 ? p.c0[(long)b * HP + j] : 0.f);
-    const float h = lstmh_fwd_gates<HP>(part, tid, p, bt, j, c);
+    const float h = lstmh_fwd_gates<HP>(part, q.tid, p, bt, j, c);
     p.y[bt * HP + j] = h;
     if (t == p.S - 1) {
         p.hN[(long)b * HP + j] = h;
         p.cN[(long)b * HP + j] = c;
     }
-}
-
-// ---- backward: K = 4 Hp, a wave's quarter is Hp = 16 * (4 KF) wide
-template <int KF> struct LstmHB {
-    static constexpr int HP = 64 * KF, GP = 4 * HP, NF = 4 * KF;        // NF fragments per lane ...
-    static constexpr int CH = NF % 16 == 0 ? 16 : 8, NCH = NF / CH;     // ... fetched and multiplied CH at a time
-};
-
-template <int KF>
-__device__ __forceinline__ void lstmh_load_whhT(float4 (&bw)[4 * KF], const float* __restrict__ whhT, int j0, int i, int koff) {
-#pragma unroll
-    for (int ii = 0; ii < 4 * KF; ++ii)
-        bw[ii] = *reinterpret_cast<const float4*>(whhT + (long)(j0 + i) * (256 * KF) + koff + 16 * ii);
-}
-
-// one piece of the contraction: fragments c0 .. c0 + CH of this lane
-template <int KF, int CH>
-__device__ __forceinline__ void lstmh_bwd_piece(f32x4& acc, const float4 (&a)[CH], const float4 (&bw)[4 * KF], int c0) {
-#pragma unroll
-    for (int ii = 0; ii < CH; ++ii)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(f4c(a[ii], jj), f4c(bw[c0 + ii], jj), acc, 0, 0, 0);
 }
 
 template <int HP>
@@ -700,40 +628,36 @@ __device__ __forceinline__ void lstmh_bwd_gates(const float (&part)[4][256], int
 
 template <int KF>
 __global__ __launch_bounds__(256) void lstmh_persist_bwd_kernel(LstmHBwd p, int spin_limit) {
-    using W = LstmHB<KF>;
+    using W = PadBwd<4, KF>;
     constexpr int HP = W::HP, GP = W::GP, CH = W::CH;
     __shared__ float part[4][256];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int i = lane & 15, kq = lane >> 4;
-    const int j0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
-    const int koff = HP * w + 4 * kq;
+    PadTile q;
+    const int koff = GP / 4 * q.w + 4 * q.kq;
     float4 bw[W::NF];
-    lstmh_load_whhT<KF>(bw, p.whhT, j0, i, koff);
-    const bool ok = (b0 + i) < p.B;
-    const int arow = ok ? b0 + i : b0;
-    const int b = b0 + (tid >> 4), j = j0 + (tid & 15);
-    const bool live = b < p.B;
+    pad_load_whhT<4, KF>(bw, p.whhT, q.j0, q.i, koff);
+    q.feed_row(p.B);
+    q.gate_thread(p.B);
     float dc = 0.f;
     int budget = spin_limit;
     PollPace pace(-1), nopace(0);                    // (the later pieces of a step follow the first at once)
     for (int t = p.S - 1; t >= 0; --t) {
         f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
         if (t < p.S - 1) {                           // (t == S - 1: dG_{t+1} = 0, the product is 0)
-            const float* row = p.dG + ((long)arow * p.S + t + 1) * GP + koff;
+            const float* row = p.dG + ((long)q.arow * p.S + t + 1) * GP + koff;
 #pragma unroll
-            for (int q = 0; q < W::NCH; ++q) {
+            for (int c = 0; c < W::NCH; ++c) {
                 float4 a[CH];
-                poll_frags<CH, 16>(row + 16 * CH * q, ok, a, budget, q == 0 ? pace : nopace, &g_lstm_poll_timeout);
-                lstmh_bwd_piece<KF, CH>(acc, a, bw, CH * q);
+                poll_frags<CH, 16>(row + 16 * CH * c, q.ok, a, budget, c == 0 ? pace : nopace, &g_lstm_poll_timeout);
+                pad_bwd_piece<W::NF, CH>(acc, a, bw, CH * c);
             }
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) part[w][(kq * 4 + r) * 16 + i] = acc[r];
+        for (int r = 0; r < 4; ++r) part[q.w][(q.kq * 4 + r) * 16 + q.i] = acc[r];
         __syncthreads();
-        if (live) {
+        if (q.live) {
             float dg[4];
-            lstmh_bwd_gates<HP>(part, tid, p, b, j, t, dc, dg);
-            float* out = p.dG + ((long)b * p.S + t) * GP + j;
+            lstmh_bwd_gates<HP>(part, q.tid, p, q.b, q.j, t, dc, dg);
+            float* out = p.dG + ((long)q.b * p.S + t) * GP + q.j;
 #pragma unroll
             for (int g = 0; g < 4; ++g) store_coherent(out + g * HP, dg[g]);
         }
@@ -743,36 +667,35 @@ __global__ __launch_bounds__(256) void lstmh_persist_bwd_kernel(LstmHBwd p, int 
 
 template <int KF>
 __global__ __launch_bounds__(256) void lstmh_step_bwd_kernel(LstmHBwd p, int t) {
-    using W = LstmHB<KF>;
+    using W = PadBwd<4, KF>;
     constexpr int HP = W::HP, GP = W::GP, CH = W::CH;
     __shared__ float part[4][256];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int i = lane & 15, kq = lane >> 4;
-    const int j0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
-    const int koff = HP * w + 4 * kq;
+    PadTile q;
+    const int koff = GP / 4 * q.w + 4 * q.kq;
     float4 bw[W::NF];
-    lstmh_load_whhT<KF>(bw, p.whhT, j0, i, koff);
-    const bool ok = (b0 + i) < p.B;
+    pad_load_whhT<4, KF>(bw, p.whhT, q.j0, q.i, koff);
+    q.feed_row(p.B);
     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
     if (t + 1 < p.S) {
-        const float* row = p.dG + ((long)(ok ? b0 + i : b0) * p.S + t + 1) * GP + koff;
+        const float* row = p.dG + ((long)q.arow * p.S + t + 1) * GP + koff;
 #pragma unroll
-        for (int q = 0; q < W::NCH; ++q) {
+        for (int c = 0; c < W::NCH; ++c) {
             float4 a[CH];
 #pragma unroll
             for (int ii = 0; ii < CH; ++ii)
-                a[ii] = ok ? *reinterpret_cast<const float4*>(row + 16 * (CH * q + ii)) : make_float4(0.f, 0.f, 0.f, 0.f);
-            lstmh_bwd_piece<KF, CH>(acc, a, bw, CH * q);
+                a[ii] = q.ok ? *reinterpret_cast<const float4*>(row + 16 * (CH * c + ii)) : make_float4(0.f, 0.f, 0.f, 0.f);
+            pad_bwd_piece<W::NF, CH>(acc, a, bw, CH * c);
         }
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) part[w][(kq * 4 + r) * 16 + i] = acc[r];
+    for (int r = 0; r < 4; ++r) part[q.w][(q.kq * 4 + r) * 16 + q.i] = acc[r];
     __syncthreads();
-    const int b = b0 + (tid >> 4), j = j0 + (tid & 15);
-    if (b >= p.B) return;
+    q.gate_thread(p.B);
+    if (!q.live) return;
+    const int b = q.b, j = q.j;
     float dc = t + 1 < p.S ? p.DC[(long)b * HP + j] : 0.f;
     float dg[4];
-    lstmh_bwd_gates<HP>(part, tid, p, b, j, t, dc, dg);
+    lstmh_bwd_gates<HP>(part, q.tid, p, b, j, t, dc, dg);
     float* out = p.dG + ((long)b * p.S + t) * GP + j;
 #pragma unroll
     for (int g = 0; g < 4; ++g) out[g * HP] = dg[g];
@@ -780,192 +703,37 @@ __global__ __launch_bounds__(256) void lstmh_step_bwd_kernel(LstmHBwd p, int t) 
 }
 
 // ------------------------------------------------------------------ host side
-static inline int lstmh_padded(int H) { return 128 * cdiv(H, 128); }
-
-struct LstmHLayout {
-    int Hp;
-    long G[8], C[8], Y[8];                                    // saved: every layer keeps its padded output
-    long saved_total;
-    long gx, wih, whh, bih, bhh, h0, c0, hN, cN, ipf, fwd_total;
-    long whhT, wihT, wihp, whhp, dG, DC, mid[2], bh0, bc0, gwih, gwhh, gbih, gbhh, part, tmp, ipb, bwd_total;
-};
-
-static bool lstmh_layout(int B, int S, int nl, int D, int H, LstmHLayout& g) {
-    if (B <= 0 || S <= 0 || nl <= 0 || nl > 8 || D < 1 || D > kInProjMaxD || H < 1 || H > 512) return false;
-    const int Hp = lstmh_padded(H), Gp = 4 * Hp;
-    const long M = (long)B * S;
-    if (M > (1L << 21) || M * Gp > (1L << 31)) return false;        // B*S*4Hp floats stay within 2^31
-    g.Hp = Hp;
-    const long mh = align64l(M * Hp), mg = align64l(M * Gp), wi = (long)Gp * (D > Hp ? D : Hp), wh = (long)Gp * Hp;
-    const long st = align64l((long)nl * B * Hp);
-    long o = 0;
-    for (int l = 0; l < nl; ++l) {
-        g.G[l] = o; o += mg;
-        g.C[l] = o; o += mh;
-        g.Y[l] = o; o += mh;
-    }
-    g.saved_total = o;
-    o = 0;
-    g.gx = o; o += mg;
-    g.wih = o; o += align64l(wi);
-    g.whh = o; o += wh;
-    g.bih = o; o += Gp;
-    g.bhh = o; o += Gp;
-    g.h0 = o; o += st;
-    g.c0 = o; o += st;
-    g.hN = o; o += st;
-    g.cN = o; o += st;
-    g.ipf = o; o += in_proj_w_floats(Gp, D);
-    g.fwd_total = o;
-    o = 0;
-    g.whhT = o; o += wh;
-    g.wihT = o; o += wh;
-    g.wihp = o; o += align64l(wi);
-    g.whhp = o; o += wh;
-    g.dG = o; o += mg;
-    g.DC = o; o += align64l((long)B * Hp);
-    g.mid[0] = o; o += mh;
-    g.mid[1] = o; o += mh;
-    g.bh0 = o; o += align64l((long)B * Hp);
-    g.bc0 = o; o += align64l((long)B * Hp);
-    g.gwih = o; o += align64l(wi);
-    g.gwhh = o; o += wh;
-    g.gbih = o; o += Gp;
-    g.gbhh = o; o += Gp;
-    g.part = o; o += align64l(tn_gemm_part_floats((int)M, Gp, Hp));
-    g.tmp = o; o += align64l((long)kRowsSumGroups * Gp);
-    g.ipb = o; o += in_proj_scratch_floats(M, Gp, D);
-    g.bwd_total = o;
-    return true;
-}
-
-static int lstmh_copy(const float* src, float* dst, int ng, long sr, int sc, long dr, int dc, hipStream_t st) {
-    const long n = (long)ng * dr * dc, blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(lstmh_copy_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, src, dst, ng, sr, sc,
-                       dr, dc);
-    CPC_LAUNCH_CHECK();
-    return 0;
-}
-
-// Which recurrence kernels the cpc_lstm_*_h calls of this process launched since the last cpc_lstm_paths_h(1):
-// bit 0 a persistent one, bit 1 the per-step ones (the residency fallback of recur_launch, or CPC_LSTM_PER_STEP).
+// Which recurrence kernels the cpc_lstm_*_h calls of this process launched since the last cpc_lstm_paths_h(1)
 static int g_lstmh_paths = 0;
 
-template <int KF>
-static int lstmh_recur_kf(const LstmHFwd& p, int per_step, hipStream_t st) {
-    bool persistent = false;
-    const int rc = recur_launch(lstmh_persist_fwd_kernel<KF>, lstmh_step_fwd_kernel<KF>, p, dim3(4 * KF, cdiv(p.B, 16)), 1, p.S,
-                                false, per_step, p.y, (size_t)p.B * p.S * 64 * KF, kLstmSpinLimit, st, &persistent);
-    g_lstmh_paths |= persistent ? 1 : 2;
-    return rc;
-}
-template <int KF>
-static int lstmh_recur_kf(const LstmHBwd& p, int per_step, hipStream_t st) {
-    bool persistent = false;
-    const int rc = recur_launch(lstmh_persist_bwd_kernel<KF>, lstmh_step_bwd_kernel<KF>, p, dim3(4 * KF, cdiv(p.B, 16)), 1, p.S,
-                                true, per_step, p.dG, (size_t)p.B * p.S * 256 * KF, kLstmSpinLimit, st, &persistent);
-    g_lstmh_paths |= persistent ? 1 : 2;
-    return rc;
-}
-// the instantiation of the padded width Hp in {128, 256, 384, 512}
-template <class Rec>
-static int lstmh_recur(const Rec& p, int Hp, int per_step, hipStream_t st) {
-    switch (Hp) {
-        case 128: return lstmh_recur_kf<2>(p, per_step, st);
-        case 256: return lstmh_recur_kf<4>(p, per_step, st);
-        case 384: return lstmh_recur_kf<6>(p, per_step, st);
-        case 512: return lstmh_recur_kf<8>(p, per_step, st);
+// The cell as padded_cell.h's layout and drivers see it.  Saved per layer: G (B,S,4Hp), C, Y; carried: h0, c0; the backward's
+// own: dG (B,S,4Hp, polled and read by the tail as both dGi and dGh), DC (B,Hp).
+struct LstmHCell {
+    static constexpr int NG = 4, NS = 2, kDGh = 0, kPerStep = CPC_LSTM_PER_STEP;
+    static constexpr const char* kSaved = "ghh";
+    static constexpr const char* kOwn = "gs";
+    using Fwd = LstmHFwd;
+    using Bwd = LstmHBwd;
+    static void fill(Fwd& p, float* saved, const long* slot, const float* const* s0, float* const* sN) {
+        p.G = saved + slot[0]; p.C = saved + slot[1];
+        p.h0 = s0[0]; p.c0 = s0[1]; p.hN = sN[0]; p.cN = sN[1];
     }
-    return CPC_ERR_SHAPE;
-}
-
-#define LSTMH_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
-
-static int lstmh_forward(const float* x, const float* h0, const float* c0, const float* const* params, float* saved,
-                         float* scratch, float* y, float* hN, float* cN, int B, int S, int nl, int D, int H, int flags,
-                         void* stream) {
-    LstmHLayout g;
-    CPC_RETURN_IF(!lstmh_layout(B, S, nl, D, H, g), CPC_ERR_SHAPE);
-    CPC_RETURN_IF(flags & ~CPC_LSTM_PER_STEP, CPC_ERR_ARG);
-    CPC_RETURN_IF(!x || !ptrs_ok(params, 4 * nl) || !saved || !scratch || !y || !hN || !cN, CPC_ERR_ARG);
-    CPC_RETURN_IF((h0 == nullptr) != (c0 == nullptr), CPC_ERR_ARG);
-    hipStream_t st = (hipStream_t)stream;
-    const int Hp = g.Hp, Gp = 4 * Hp, M = B * S;
-    if (h0) {
-        LSTMH_TRY(lstmh_copy(h0, scratch + g.h0, 1, (long)nl * B, H, (long)nl * B, Hp, st));
-        LSTMH_TRY(lstmh_copy(c0, scratch + g.c0, 1, (long)nl * B, H, (long)nl * B, Hp, st));
+    static void fill(Bwd& p, const float* saved, const long* slot, const float* const* s0, float* scratch, const long* own) {
+        p.G = saved + slot[0]; p.C = saved + slot[1];
+        p.c0 = s0[1];
+        p.dG = scratch + own[0]; p.DC = scratch + own[1];
     }
-    const float* in = x;
-    for (int l = 0; l < nl; ++l) {
-        const int Dl = l == 0 ? D : H, Dlp = l == 0 ? D : Hp;          // true and internal width of this layer's input
-        LSTMH_TRY(lstmh_copy(params[4 * l], scratch + g.wih, 4, H, Dl, Hp, Dlp, st));
-        LSTMH_TRY(lstmh_copy(params[4 * l + 1], scratch + g.whh, 4, H, H, Hp, Hp, st));
-        LSTMH_TRY(lstmh_copy(params[4 * l + 2], scratch + g.bih, 4, 1, H, 1, Hp, st));
-        LSTMH_TRY(lstmh_copy(params[4 * l + 3], scratch + g.bhh, 4, 1, H, 1, Hp, st));
-        LSTMH_TRY(layer_input_projection(l, D, in, scratch + g.wih, scratch + g.bih, scratch + g.ipf, scratch + g.gx, M, Gp, st, Hp));
-        LstmHFwd p;
-        p.gx = scratch + g.gx; p.whh = scratch + g.whh; p.bhh = scratch + g.bhh;
-        p.h0 = h0 ? scratch + g.h0 + (long)l * B * Hp : nullptr;
-        p.c0 = c0 ? scratch + g.c0 + (long)l * B * Hp : nullptr;
-        p.y = saved + g.Y[l]; p.G = saved + g.G[l]; p.C = saved + g.C[l];
-        p.hN = scratch + g.hN + (long)l * B * Hp;
-        p.cN = scratch + g.cN + (long)l * B * Hp;
-        p.B = B; p.S = S; p.g0 = 0;
-        LSTMH_TRY(lstmh_recur(p, Hp, flags & CPC_LSTM_PER_STEP, st));
-        in = p.y;
+    template <int KF>
+    static int recur(const Fwd& p, int per_step, hipStream_t st) {
+        return padded_recur_kf(lstmh_persist_fwd_kernel<KF>, lstmh_step_fwd_kernel<KF>, p, KF, false, p.y, 1, kLstmSpinLimit,
+                               per_step, &g_lstmh_paths, st);
     }
-    LSTMH_TRY(lstmh_copy(in, y, 1, M, Hp, M, H, st));
-    LSTMH_TRY(lstmh_copy(scratch + g.hN, hN, 1, (long)nl * B, Hp, (long)nl * B, H, st));
-    return lstmh_copy(scratch + g.cN, cN, 1, (long)nl * B, Hp, (long)nl * B, H, st);
-}
-
-static int lstmh_backward(const float* x, const float* h0, const float* c0, const float* const* params, const float* saved,
-                          const float* y, const float* dy, float* scratch, float* dx, float* const* grads, int B, int S, int nl,
-                          int D, int H, int flags, void* stream) {
-    LstmHLayout g;
-    CPC_RETURN_IF(!lstmh_layout(B, S, nl, D, H, g), CPC_ERR_SHAPE);
-    CPC_RETURN_IF(flags & ~CPC_LSTM_PER_STEP, CPC_ERR_ARG);
-    CPC_RETURN_IF(!x || !ptrs_ok(params, 4 * nl) || !saved || !y || !dy || !scratch || !dx ||
-                  !ptrs_ok(const_cast<const float* const*>(grads), 4 * nl), CPC_ERR_ARG);
-    CPC_RETURN_IF((h0 == nullptr) != (c0 == nullptr), CPC_ERR_ARG);
-    hipStream_t st = (hipStream_t)stream;
-    const int Hp = g.Hp, Gp = 4 * Hp, M = B * S;
-    // dy at the padded width in the mid[] slot the top layer does not write (the layer below it may: dy is spent by then)
-    float* dyp = scratch + g.mid[nl & 1];
-    LSTMH_TRY(lstmh_copy(dy, dyp, 1, M, H, M, Hp, st));
-    const float* dYl = dyp;
-    for (int l = nl - 1; l >= 0; --l) {
-        const int Dl = l == 0 ? D : H, Dlp = l == 0 ? D : Hp;
-        LSTMH_TRY(lstmh_copy(params[4 * l], scratch + g.wihp, 4, H, Dl, Hp, Dlp, st));
-        LSTMH_TRY(lstmh_copy(params[4 * l + 1], scratch + g.whhp, 4, H, H, Hp, Hp, st));
-        if (h0) {
-            LSTMH_TRY(lstmh_copy(h0 + (long)l * B * H, scratch + g.bh0, 1, B, H, B, Hp, st));
-            LSTMH_TRY(lstmh_copy(c0 + (long)l * B * H, scratch + g.bc0, 1, B, H, B, Hp, st));
-        }
-        const float* wp[4] = {scratch + g.wihp, scratch + g.whhp, nullptr, nullptr};      // (the tail reads no bias)
-        float* gp[4] = {scratch + g.gwih, scratch + g.gwhh, scratch + g.gbih, scratch + g.gbhh};
-        GradTail t;
-        t.H = Hp; t.N = Gp; t.G = 1; t.T = S; t.R = B; t.D = Dlp; t.time_major = false;
-        t.dGi = t.dGh = scratch + g.dG; t.in = l == 0 ? x : saved + g.Y[l - 1]; t.out = saved + g.Y[l];
-        t.h0 = h0 ? scratch + g.bh0 : nullptr;
-        t.w = wp; t.dw = gp; t.dx = l == 0 ? dx : scratch + g.mid[l & 1];
-        t.whhT = scratch + g.whhT; t.wihT = scratch + g.wihT; t.part = scratch + g.part; t.tmp = scratch + g.tmp;
-        t.ip_scratch = scratch + g.ipb;
-        LSTMH_TRY(tail_transposes(t, st));
-        LstmHBwd p;
-        p.whhT = t.whhT; p.dY = dYl; p.G = saved + g.G[l]; p.C = saved + g.C[l];
-        p.c0 = c0 ? scratch + g.bc0 : nullptr;
-        p.dG = scratch + g.dG; p.DC = scratch + g.DC; p.B = B; p.S = S; p.g0 = 0;
-        LSTMH_TRY(lstmh_recur(p, Hp, flags & CPC_LSTM_PER_STEP, st));
-        LSTMH_TRY(tail_gradients(t, st));
-        LSTMH_TRY(lstmh_copy(gp[0], grads[4 * l], 4, Hp, Dlp, H, Dl, st));
-        LSTMH_TRY(lstmh_copy(gp[1], grads[4 * l + 1], 4, Hp, Hp, H, H, st));
-        LSTMH_TRY(lstmh_copy(gp[2], grads[4 * l + 2], 4, 1, Hp, 1, H, st));
-        LSTMH_TRY(lstmh_copy(gp[3], grads[4 * l + 3], 4, 1, Hp, 1, H, st));
-        dYl = t.dx;
+    template <int KF>
+    static int recur(const Bwd& p, int per_step, hipStream_t st) {
+        return padded_recur_kf(lstmh_persist_bwd_kernel<KF>, lstmh_step_bwd_kernel<KF>, p, KF, true, p.dG, NG, kLstmSpinLimit,
+                               per_step, &g_lstmh_paths, st);
     }
-    return 0;
-}
+};
 
 }  // namespace cpc
 
@@ -978,20 +746,24 @@ extern "C" int cpc_lstm_paths_h(int clear) {
 
 extern "C" int cpc_lstm_layout_h(int B, int S, int nl, int D, int H, long* sizes) {
     if (H == kLH) return cpc_lstm_layout_in(B, S, nl, D, sizes);
-    LstmHLayout g;
-    return layout_sizes(lstmh_layout(B, S, nl, D, H, g), g, sizes);
+    PaddedLayout g;
+    return layout_sizes(padded_layout<LstmHCell>(B, S, nl, D, H, g), g, sizes);
 }
 
 extern "C" int cpc_lstm_forward_h(const float* x, const float* h0, const float* c0, const float* const* params, float* saved,
                                   float* scratch, float* y, float* hN, float* cN, int B, int S, int nl, int D, int H, int flags,
                                   void* stream) {
     if (H == kLH) return cpc_lstm_forward_in(x, h0, c0, params, saved, scratch, y, hN, cN, B, S, nl, D, flags, stream);
-    return lstmh_forward(x, h0, c0, params, saved, scratch, y, hN, cN, B, S, nl, D, H, flags, stream);
+    const float* st0[2] = {h0, c0};
+    float* stN[2] = {hN, cN};
+    return padded_forward<LstmHCell>(x, st0, params, saved, scratch, y, stN, B, S, nl, D, H, flags, stream);
 }
 
 extern "C" int cpc_lstm_backward_h(const float* x, const float* h0, const float* c0, const float* const* params,
                                    const float* saved, const float* y, const float* dy, float* scratch, float* dx,
                                    float* const* grads, int B, int S, int nl, int D, int H, int flags, void* stream) {
     if (H == kLH) return cpc_lstm_backward_in(x, h0, c0, params, saved, y, dy, scratch, dx, grads, B, S, nl, D, flags, stream);
-    return lstmh_backward(x, h0, c0, params, saved, y, dy, scratch, dx, grads, B, S, nl, D, H, flags, stream);
+    const float* st0[2] = {h0, c0};
+    return padded_backward<LstmHCell>(x, st0, params, saved, y, dy, scratch, dx, grads, B, S, nl, D, H, flags, stream);
 }
+

@@ -2,7 +2,8 @@
 // every cell -- the input projection of a layer in front of it, the gradient GEMMs and reductions over all rows behind the
 // backward one, and the choice between one persistent launch and one launch per step.  No device code here: the kernels and the
 // structs they take stay with their cell.  H = kC = 256 is the hidden size of all three; the LSTM and the GRU at another hidden
-// width (lstm.hip: cpc_lstm_*_h, gru.hip: cpc_gru_*_h) pass their padded width instead.
+// width (lstm.hip: cpc_lstm_*_h, gru.hip: cpc_gru_*_h) pass their padded width instead, from padded_cell.h, which holds what
+// those two share -- device helpers included -- and drives this header's functions for them.
 #pragma once
 #include "cpc_common.h"
 #include "cpc_internal.h"

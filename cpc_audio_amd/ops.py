@@ -345,6 +345,15 @@ def _layout(kind, fn, n, *args):
     return v
 
 
+def _layout_takes(kind, *args):
+    """Does the layout entry cpc_<kind> take this shape?  (_layout raises ValueError for one it refuses)"""
+    try:
+        _layout(kind, getattr(_lib.get(), "cpc_" + kind), 3, *(int(a) for a in args))
+    except ValueError:
+        return False
+    return True
+
+
 def saved_encoder_activations(saved, B, L):
     """fp32 copies (B, L_i, 256) of the four intermediate activations y0..y3 an EncoderFunction forward left in ``saved``
     (layers 0 and 1 are kept as two fp16 pieces per element in the default mode).  Parity tests only."""
@@ -663,6 +672,68 @@ class LstmFunction(torch.autograd.Function):
         return (dx, None, None, *grads)
 
 
+def _hidden_forward(ctx, cell, ng, x, states, per_step, params):
+    """forward of GruHiddenFunction (cell "gru", ng = 3) and LstmHiddenFunction ("lstm", 4): checks, allocation and the
+    cpc_<cell>_forward_h call.  states: the carried (nl,B,H) tensors -- h0, for the LSTM also c0 -- all None or all given; one
+    final state per carried one comes back behind y."""
+    name, mod = f"{cell.capitalize()}HiddenFunction", cell.upper()
+    _require_cuda(x, name)
+    lib = _lib.get()
+    nl = len(params) // 4
+    if x.dim() != 3 or nl < 1 or len(params) != 4 * nl or params[1].dim() != 2 or params[0].dim() != 2:
+        raise NotImplementedError(f"cpc_audio_amd.{name}: x (B,S,D) and 4 parameters per nn.{mod} layer expected")
+    B, S, D = x.shape
+    H = params[1].shape[1]
+    shapes = []
+    for l in range(nl):
+        shapes += [(ng * H, D if l == 0 else H), (ng * H, H), (ng * H,), (ng * H,)]
+    if [tuple(p.shape) for p in params] != shapes or x.dtype != torch.float32:
+        raise NotImplementedError(f"cpc_audio_amd.{name}: fp32 nn.{mod}({D}, {H}, {nl}) parameters expected, got "
+                                  f"{[tuple(p.shape) for p in params]}")
+    x = x.contiguous()
+    params = [p.detach().contiguous() for p in params]
+    states = [None if s is None else s.detach().contiguous() for s in states]
+    if states[0] is not None and any(tuple(s.shape) != (nl, B, H) for s in states):
+        raise NotImplementedError(f"cpc_audio_amd.{name}: carried state of shape {(nl, B, H)} expected")
+    flags = 1 if per_step else 0                      # CPC_GRU_PER_STEP, CPC_LSTM_PER_STEP
+    with torch.cuda.device(x.device):
+        sizes = _layout(f"{cell}_layout_h", getattr(lib, f"cpc_{cell}_layout_h"), 3, B, S, nl, D, H)
+        saved = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
+        scratch = torch.empty(sizes[1], device=x.device, dtype=torch.float32)
+        y = torch.empty(B, S, H, device=x.device, dtype=torch.float32)
+        finals = [torch.empty(nl, B, H, device=x.device, dtype=torch.float32) for _ in states]
+        lib.check(getattr(lib, f"cpc_{cell}_forward_h")(_p(x), *(_p(s) for s in states), _ptrs(params), _p(saved), _p(scratch),
+                                                        _p(y), *(_p(f) for f in finals), B, S, nl, D, H, flags, _stream()),
+                  f"{cell}_forward_h")
+    ctx.save_for_backward(x, saved, y, *params)
+    ctx.states = states
+    ctx.dims = (B, S, nl, D, H, sizes[2], flags)
+    ctx.mark_non_differentiable(*finals)
+    ctx.set_materialize_grads(False)
+    return (y, *finals)
+
+
+def _hidden_backward(ctx, cell, dy):
+    """backward of the two: the cpc_<cell>_backward_h call -> (dx, None for the carried state, None for per_step, *grads)"""
+    lib = _lib.get()
+    x, saved, y, *params = ctx.saved_tensors
+    B, S, nl, D, H, nscr, flags = ctx.dims
+    dy = torch.zeros_like(y) if dy is None else dy.contiguous()
+    with torch.cuda.device(x.device):
+        scratch = torch.empty(nscr, device=x.device, dtype=torch.float32)
+        dx = torch.empty_like(x)
+        grads = [torch.empty_like(p) for p in params]
+        lib.check(getattr(lib, f"cpc_{cell}_backward_h")(_p(x), *(_p(s) for s in ctx.states), _ptrs(params), _p(saved), _p(y),
+                                                         _p(dy), _p(scratch), _p(dx), _ptrs(grads), B, S, nl, D, H, flags,
+                                                         _stream()), f"{cell}_backward_h")
+    return (dx, None, None, *grads)
+
+
+def _hidden_paths(cell, clear):
+    mask = getattr(_lib.get(), f"cpc_{cell}_paths_h")(1 if clear else 0)
+    return {name for bit, name in ((1, "persistent"), (2, "per_step")) if mask & bit}
+
+
 class LstmHiddenFunction(torch.autograd.Function):
     """nn.LSTM(D, H, nl, batch_first=True) at any hidden width: x (B,S,D), state None or (h0, c0) (each (nl,B,H)), 4*nl LSTM
     parameters at their true shapes -> y (B,S,H), (hN, cN) (each (nl,B,H)), 1 <= D, H <= 512 (cpc_lstm_forward_h / _backward_h:
@@ -672,71 +743,22 @@ class LstmHiddenFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, state, per_step, *params):
-        _require_cuda(x, "LstmHiddenFunction")
-        lib = _lib.get()
-        nl = len(params) // 4
-        if x.dim() != 3 or nl < 1 or len(params) != 4 * nl or params[1].dim() != 2 or params[0].dim() != 2:
-            raise NotImplementedError("cpc_audio_amd.LstmHiddenFunction: x (B,S,D) and 4 parameters per nn.LSTM layer expected")
-        B, S, D = x.shape
-        H = params[1].shape[1]
-        shapes = []
-        for l in range(nl):
-            shapes += [(4 * H, D if l == 0 else H), (4 * H, H), (4 * H,), (4 * H,)]
-        if [tuple(p.shape) for p in params] != shapes or x.dtype != torch.float32:
-            raise NotImplementedError(f"cpc_audio_amd.LstmHiddenFunction: fp32 nn.LSTM({D}, {H}, {nl}) parameters expected, got "
-                                      f"{[tuple(p.shape) for p in params]}")
-        x = x.contiguous()
-        params = [p.detach().contiguous() for p in params]
-        h0, c0 = (None, None) if state is None else (state[0].detach().contiguous(), state[1].detach().contiguous())
-        if h0 is not None and (tuple(h0.shape) != (nl, B, H) or tuple(c0.shape) != (nl, B, H)):
-            raise NotImplementedError(f"cpc_audio_amd.LstmHiddenFunction: carried state of shape {(nl, B, H)} expected")
-        flags = 1 if per_step else 0                      # CPC_LSTM_PER_STEP
-        with torch.cuda.device(x.device):
-            sizes = _layout("lstm_layout_h", lib.cpc_lstm_layout_h, 3, B, S, nl, D, H)
-            saved = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
-            scratch = torch.empty(sizes[1], device=x.device, dtype=torch.float32)
-            y = torch.empty(B, S, H, device=x.device, dtype=torch.float32)
-            hN = torch.empty(nl, B, H, device=x.device, dtype=torch.float32)
-            cN = torch.empty(nl, B, H, device=x.device, dtype=torch.float32)
-            lib.check(lib.cpc_lstm_forward_h(_p(x), _p(h0), _p(c0), _ptrs(params), _p(saved), _p(scratch), _p(y), _p(hN), _p(cN),
-                                             B, S, nl, D, H, flags, _stream()), "lstm_forward_h")
-        ctx.save_for_backward(x, saved, y, *params)
-        ctx.state = (h0, c0)
-        ctx.dims = (B, S, nl, D, H, sizes[2], flags)
-        ctx.mark_non_differentiable(hN, cN)
-        ctx.set_materialize_grads(False)
-        return y, hN, cN
+        return _hidden_forward(ctx, "lstm", 4, x, (None, None) if state is None else state, per_step, params)
 
     @staticmethod
     def backward(ctx, dy, _dhN, _dcN):
-        lib = _lib.get()
-        x, saved, y, *params = ctx.saved_tensors
-        B, S, nl, D, H, nscr, flags = ctx.dims
-        h0, c0 = ctx.state
-        dy = torch.zeros_like(y) if dy is None else dy.contiguous()
-        with torch.cuda.device(x.device):
-            scratch = torch.empty(nscr, device=x.device, dtype=torch.float32)
-            dx = torch.empty_like(x)
-            grads = [torch.empty_like(p) for p in params]
-            lib.check(lib.cpc_lstm_backward_h(_p(x), _p(h0), _p(c0), _ptrs(params), _p(saved), _p(y), _p(dy), _p(scratch), _p(dx),
-                                              _ptrs(grads), B, S, nl, D, H, flags, _stream()), "lstm_backward_h")
-        return (dx, None, None, *grads)
+        return _hidden_backward(ctx, "lstm", dy)
 
 
 def lstm_hidden_paths(clear=True):
     """Which recurrence kernels LstmHiddenFunction has launched since the last clearing call: a set out of "persistent" and
     "per_step" (cpc_lstm_paths_h; per_step is the residency fallback of a grid that cannot be co-resident, or the flag)."""
-    mask = _lib.get().cpc_lstm_paths_h(1 if clear else 0)
-    return {name for bit, name in ((1, "persistent"), (2, "per_step")) if mask & bit}
+    return _hidden_paths("lstm", clear)
 
 
 def lstm_hidden_supported(B, S, nl, D, H):
     """Does cpc_lstm_layout_h take nn.LSTM(D, H, nl) on (B, S, D)?"""
-    try:
-        _layout("lstm_layout_h", _lib.get().cpc_lstm_layout_h, 3, int(B), int(S), int(nl), int(D), int(H))
-    except ValueError:
-        return False
-    return True
+    return _layout_takes("lstm_layout_h", B, S, nl, D, H)
 
 
 GRU_HIDDEN_MAX = 512   # widest hidden state of the GRU at any hidden width (cpc_gru_*_h; csrc/gru.hip)
@@ -751,78 +773,27 @@ class GruHiddenFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h0, per_step, *params):
-        _require_cuda(x, "GruHiddenFunction")
-        lib = _lib.get()
-        nl = len(params) // 4
-        if x.dim() != 3 or nl < 1 or len(params) != 4 * nl or params[1].dim() != 2 or params[0].dim() != 2:
-            raise NotImplementedError("cpc_audio_amd.GruHiddenFunction: x (B,S,D) and 4 parameters per nn.GRU layer expected")
-        B, S, D = x.shape
-        H = params[1].shape[1]
-        shapes = []
-        for l in range(nl):
-            shapes += [(3 * H, D if l == 0 else H), (3 * H, H), (3 * H,), (3 * H,)]
-        if [tuple(p.shape) for p in params] != shapes or x.dtype != torch.float32:
-            raise NotImplementedError(f"cpc_audio_amd.GruHiddenFunction: fp32 nn.GRU({D}, {H}, {nl}) parameters expected, got "
-                                      f"{[tuple(p.shape) for p in params]}")
-        x = x.contiguous()
-        params = [p.detach().contiguous() for p in params]
-        h0 = None if h0 is None else h0.detach().contiguous()
-        if h0 is not None and tuple(h0.shape) != (nl, B, H):
-            raise NotImplementedError(f"cpc_audio_amd.GruHiddenFunction: carried state of shape {(nl, B, H)} expected")
-        flags = 1 if per_step else 0                      # CPC_GRU_PER_STEP
-        with torch.cuda.device(x.device):
-            sizes = _layout("gru_layout_h", lib.cpc_gru_layout_h, 3, B, S, nl, D, H)
-            saved = torch.empty(sizes[0], device=x.device, dtype=torch.float32)
-            scratch = torch.empty(sizes[1], device=x.device, dtype=torch.float32)
-            y = torch.empty(B, S, H, device=x.device, dtype=torch.float32)
-            hN = torch.empty(nl, B, H, device=x.device, dtype=torch.float32)
-            lib.check(lib.cpc_gru_forward_h(_p(x), _p(h0), _ptrs(params), _p(saved), _p(scratch), _p(y), _p(hN), B, S, nl, D, H,
-                                            flags, _stream()), "gru_forward_h")
-        ctx.save_for_backward(x, saved, y, *params)
-        ctx.h0 = h0
-        ctx.dims = (B, S, nl, D, H, sizes[2], flags)
-        ctx.mark_non_differentiable(hN)
-        ctx.set_materialize_grads(False)
-        return y, hN
+        return _hidden_forward(ctx, "gru", 3, x, (h0,), per_step, params)
 
     @staticmethod
     def backward(ctx, dy, _dhN):
-        lib = _lib.get()
-        x, saved, y, *params = ctx.saved_tensors
-        B, S, nl, D, H, nscr, flags = ctx.dims
-        dy = torch.zeros_like(y) if dy is None else dy.contiguous()
-        with torch.cuda.device(x.device):
-            scratch = torch.empty(nscr, device=x.device, dtype=torch.float32)
-            dx = torch.empty_like(x)
-            grads = [torch.empty_like(p) for p in params]
-            lib.check(lib.cpc_gru_backward_h(_p(x), _p(ctx.h0), _ptrs(params), _p(saved), _p(y), _p(dy), _p(scratch), _p(dx),
-                                             _ptrs(grads), B, S, nl, D, H, flags, _stream()), "gru_backward_h")
-        return (dx, None, None, *grads)
+        return _hidden_backward(ctx, "gru", dy)
 
 
 def gru_hidden_paths(clear=True):
     """Which recurrence kernels GruHiddenFunction has launched since the last clearing call: a set out of "persistent" and
     "per_step" (cpc_gru_paths_h; per_step is the residency fallback of a grid that cannot be co-resident, or the flag)."""
-    mask = _lib.get().cpc_gru_paths_h(1 if clear else 0)
-    return {name for bit, name in ((1, "persistent"), (2, "per_step")) if mask & bit}
+    return _hidden_paths("gru", clear)
 
 
 def gru_hidden_supported(B, S, nl, D, H):
     """Does cpc_gru_layout_h take nn.GRU(D, H, nl) on (B, S, D)?"""
-    try:
-        _layout("gru_layout_h", _lib.get().cpc_gru_layout_h, 3, int(B), int(S), int(nl), int(D), int(H))
-    except ValueError:
-        return False
-    return True
+    return _layout_takes("gru_layout_h", B, S, nl, D, H)
 
 
 def lstm_supported(B, S, nl=1):
     """Does cpc_lstm_layout take nl layers on (B, S, 256)?"""
-    try:
-        _layout("lstm_layout", _lib.get().cpc_lstm_layout, 3, int(B), int(S), int(nl))
-    except ValueError:
-        return False
-    return True
+    return _layout_takes("lstm_layout", B, S, nl)
 
 
 class LstmGroupFunction(torch.autograd.Function):
@@ -873,11 +844,7 @@ class LstmGroupFunction(torch.autograd.Function):
 
 def lstm_group_supported(B, S, G):
     """Does cpc_lstm_group_layout take G heads on (B, S, 256)?"""
-    try:
-        _layout("lstm_group_layout", _lib.get().cpc_lstm_group_layout, 3, int(B), int(S), int(G))
-    except ValueError:
-        return False
-    return True
+    return _layout_takes("lstm_group_layout", B, S, G)
 
 
 class RnnFunction(torch.autograd.Function):
@@ -955,11 +922,7 @@ class RnnFunction(torch.autograd.Function):
 
 def rnn_supported(T, R, G=1, nl=1):
     """Does cpc_rnn_layout take T steps of R rows, G heads and nl layers?"""
-    try:
-        _layout("rnn_layout", _lib.get().cpc_rnn_layout, 3, int(T), int(R), int(G), int(nl))
-    except ValueError:
-        return False
-    return True
+    return _layout_takes("rnn_layout", T, R, G, nl)
 
 
 CTC_MAX_SEQ = 512        # cpc_ctc_forward: longest sequence (frames) the one-workgroup recursion holds in LDS
@@ -1255,11 +1218,7 @@ def pred_conv_layout(B, W, G, ks):
 def pred_conv_supported(B, W, G, ks):
     """The shapes cpc_pred_conv_forward / _backward take: 1 <= G <= 64 heads, 1 <= ks <= 16 taps, B, W >= 1 and
     B W G 256 < 2^31."""
-    try:
-        pred_conv_layout(B, W, G, ks)
-    except ValueError:
-        return False
-    return True
+    return _layout_takes("pred_conv_layout", B, W, G, ks)
 
 
 class PredConvFunction(torch.autograd.Function):
