@@ -93,6 +93,10 @@ SIGNATURES = {
     "cpc_encoder_forward_c": (_I, [_P] * 5 + [_I, _I, _I, _P]),
     "cpc_encoder_backward_c": (_I, [_P] * 7 + [_I, _I, _I, _P]),
     "cpc_encoder_saved_activation_c": (_I, [_P, _I, _P, _I, _I, _I, _P]),
+    "cpc_encoder_layout_n": (_I, [_I, _I, _I, _I, _I, _P]),
+    "cpc_encoder_forward_n": (_I, [_P] * 6 + [_I, _I, _I, _I, _I, _F, _F, _P]),
+    "cpc_encoder_backward_n": (_I, [_P] * 7 + [_I, _I, _I, _I, _I, _P]),
+    "cpc_encoder_saved_activation_n": (_I, [_P, _I, _P, _I, _I, _I, _I, _P]),
     "cpc_set_conv_tile": (_I, [_I]),
     "cpc_set_gru_mode": (_I, [_I]),
     "cpc_set_gru_spin_limit": (_I, [_I]),

@@ -613,6 +613,9 @@ def parse_args(argv):
     p.add_argument("--strict", action="store_true")
     p.add_argument("--file_extension", type=str, default=".wav")
     p.add_argument("--get_encoded", action="store_true")
+    p.add_argument("--encoderKernel", action="store_true", default=argparse.SUPPRESS,
+                   help="The convolutional encoder on the HIP kernels at every width from 2 to 512 and under every normMode the checkpoint "
+                        "was trained with (off by default: 256 channels under layerNorm only, everything else on torch ops).")
     p = sub.add_parser("from_pre_computed")
     _base_args(p)
     p.add_argument("path_features", type=str, help="Directory of pre-computed (1, frames, D) features (.pt or .npy)")
@@ -636,7 +639,8 @@ def _checkpoint_feature_function(args):
                               nLevelsGRU=saved.get("nLevelsGRU", 1), arMode=saved.get("arMode", "LSTM"),
                               reverse=saved.get("cpc_mode") == "reverse", sizeWindow=saved.get("sizeWindow", 20480),
                               abspos=saved.get("abspos", False), encoder_type=saved.get("encoder_type", "cpc"),
-                              mfccKernel=True)
+                              mfccKernel=True, normMode=saved.get("normMode", "layerNorm"),
+                              encoderKernel=getattr(args, "encoderKernel", False))
     harness.load_checkpoint(str(ckpt), model)
     model.gAR.keepHidden = True
     maker = harness.FeatureModule(model, args.get_encoded).cuda().eval()

@@ -82,6 +82,9 @@ def parse_args(argv):
                         help="With --addCriterion: the classifier and its softmax / one-hot as torch ops")
     parser.add_argument('--wideKernel', action='store_true', default=argparse.SUPPRESS,
                         help="With --addCriterion: the HIP call at any feature width from 1 to 512 (off by default: 256 only)")
+    parser.add_argument('--encoderKernel', action='store_true', default=argparse.SUPPRESS,
+                        help="The convolutional encoder on the HIP kernels at every width from 2 to 512 and under every normMode the checkpoint "
+                             "was trained with (off by default: 256 channels under layerNorm only, everything else on torch ops).")
     return parser.parse_args(argv)
 
 
@@ -99,7 +102,7 @@ def main(argv):
         json.dump(vars(args), file, indent=2)
 
     outData = [x[1] for x in findAllSeqs(args.pathDB, extension=args.extension, loadCache=False)[0]]
-    model = loadModel([args.pathCheckpoint])[0]
+    model = loadModel([args.pathCheckpoint], encoderKernel=getattr(args, "encoderKernel", False))[0]
     stepSize = model.gEncoder.DOWNSAMPLING / 16000
     print(f"stepSize : {stepSize}")
     featureMaker = FeatureModule(model, args.getEncoded)

@@ -433,6 +433,8 @@ def get_PER_args(args):
         args.wideKernel = True
     if data.get("hiddenKernel", False):
         args.hiddenKernel = True
+    if data.get("encoderKernel", False):
+        args.encoderKernel = True
     return args
 
 
@@ -476,6 +478,10 @@ def parse_args(argv):
     t.add_argument('--hiddenKernel', action='store_true', default=argparse.SUPPRESS,
                    help="With --hipFront --wideKernel --LSTM: the LSTM at a feature width other than 256 on the HIP kernels too "
                    "(off by default: nn.LSTM there); per reads it back from the training run's arguments")
+    t.add_argument('--encoderKernel', action='store_true', default=argparse.SUPPRESS,
+                   help="The convolutional encoder on the HIP kernels at every width from 2 to 512 and under every normMode the checkpoint "
+                   "was trained with (off by default: 256 channels under layerNorm only, everything else on torch ops); per reads "
+                   "it back from the training run's arguments")
     p = sub.add_parser('per')
     p.add_argument('output', type=str)
     p.add_argument('--batchSize', type=int, default=8)
@@ -491,8 +497,9 @@ def parse_args(argv):
     return args
 
 
-def load_feature_maker(path_checkpoint, no_pretraining=False, in_dim=1):
-    """-> (module, feature width, downsampling factor).  'ID': pre-computed features."""
+def load_feature_maker(path_checkpoint, no_pretraining=False, in_dim=1, encoderKernel=False):
+    """-> (module, feature width, downsampling factor).  'ID': pre-computed features.  encoderKernel is build_model's; the
+    checkpoint's normMode is read from its saved arguments."""
     if path_checkpoint == 'ID':
         return IDModule(), in_dim, 1
     from . import harness, train
@@ -503,7 +510,8 @@ def load_feature_maker(path_checkpoint, no_pretraining=False, in_dim=1):
                               nLevelsGRU=saved.get("nLevelsGRU", 1), arMode=saved.get("arMode", "LSTM"),
                               reverse=saved.get("cpc_mode") == "reverse", sizeWindow=saved.get("sizeWindow", 20480),
                               abspos=saved.get("abspos", False), encoder_type=saved.get("encoder_type", "cpc"),
-                              mfccKernel=True)
+                              mfccKernel=True, normMode=saved.get("normMode", "layerNorm"),
+                              encoderKernel=encoderKernel)
     if not no_pretraining:
         harness.load_checkpoint(str(ckpt), model)
     width = saved.get("hiddenEncoder", 256) if saved.get("arMode", "LSTM") == "no_ar" else saved.get("hiddenGar", 256)
@@ -556,7 +564,8 @@ def _main(args):
     if args.debug:
         seq_val = seq_val[:100]
 
-    feature_maker, hidden_gar, downsampling_factor = load_feature_maker(args.pathCheckpoint, args.no_pretraining, args.in_dim)
+    feature_maker, hidden_gar, downsampling_factor = load_feature_maker(args.pathCheckpoint, args.no_pretraining, args.in_dim,
+                                                                           encoderKernel=getattr(args, "encoderKernel", False))
     feature_maker.cuda()
     phone_criterion = CTCphone_criterion(hidden_gar, n_phones, args.LSTM, seqNorm=args.seqNorm, dropout=args.dropout,
                                          reduction=args.loss_reduction, hipHead=args.hipHead, hipFront=args.hipFront,

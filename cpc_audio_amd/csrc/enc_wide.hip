@@ -19,6 +19,8 @@
 //     splits' partial tiles are summed in index order by ew_dw_reduce_kernel.
 //   * the column sums (norm weight, norm bias, conv bias) leave ew_norm_bwd_kernel as per-workgroup partials, summed in index order.
 // No float atomics, no hand-over between workgroups: two runs give the same bits.  Offsets into activations are 64-bit.
+// The second half of the file runs the reference's other normModes -- batchNorm, instanceNorm, ID -- on the same storage and
+// GEMMs at every C in 2..512, 256 included (cpc_encoder_*_n).
 #include "cpc_common.h"
 #include "cpc_internal.h"
 
@@ -65,7 +67,11 @@ __global__ __launch_bounds__(256) void ew_pad_wd_kernel(const float* __restrict_
 
 // The overlapping-row NT GEMM.  GEMM row m = (b, v), v < V; its A row is the taps * Cp floats of X that start at row v s - p of
 // sequence b (Lx rows per sequence; rows outside are zeros); B = Wp + z wz, (Cp, taps Cp) row-major; the result (+ bias) goes to row
-// u = v os + oo + z of sequence b of `out` (Lo rows per sequence) when 0 <= u < Lo.  grid = (ceil(M / 128), Cp / 64, phases)
+// u = v os + oo + z of sequence b of `out` (Lo rows per sequence) when 0 <= u < Lo.  grid = (ceil(M / 128), Cp / 64, phases).
+// kSplitK (the forward convs of batchNorm / instanceNorm / ID): every 128 k the accumulators are folded into a second
+// set, so a rounding error grows with sqrt(128) + sqrt(K / 128) steps instead of sqrt(K) -- a statistic over as few as four rows
+// multiplies the conv's error by up to rstd.  Without it the kernel is what it was, to the bit.
+template <bool kSplitK>
 __global__ __launch_bounds__(256) void ew_gemm_kernel(const float* __restrict__ X, int Lx, int taps, int s, int p,
                                                       const float* __restrict__ Wp, long wz, const float* __restrict__ bias,
                                                       float* __restrict__ out, int Lo, int os, int oo, int V, long M, int Cp, int C) {
@@ -112,6 +118,13 @@ __global__ __launch_bounds__(256) void ew_gemm_kernel(const float* __restrict__ 
     for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 tot[kSplitK ? 2 : 1][kSplitK ? 4 : 1];
+    if (kSplitK) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) tot[kSplitK ? t : 0][kSplitK ? j : 0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     fetch(0);
     for (int k0 = 0; k0 < K; k0 += 32) {
 #pragma unroll
@@ -142,7 +155,24 @@ __global__ __launch_bounds__(256) void ew_gemm_kernel(const float* __restrict__ 
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acc[t][j] = ew_mfma(ew_elem(al[j], ah[j], kk), b, acc[t][j]);
             }
+        if (kSplitK && ((k0 & 96) == 96 || k0 + 32 >= K)) {
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    f32x4& o = tot[kSplitK ? t : 0][kSplitK ? j : 0];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) o[r] += acc[t][j][r];      // (component by component: build.py's packed-fp32 gate)
+                    acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+        }
         __syncthreads();
+    }
+    if (kSplitK) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[t][j] = tot[kSplitK ? t : 0][kSplitK ? j : 0];
     }
     // acc[t][j][r] = result[m0 + 32 w + 16 t + i][n0 + 16 j + 4 kq + r]
 #pragma unroll
@@ -605,7 +635,7 @@ static int ew_forward(const float* wave, const float* const* P, float* saved, fl
         float* wp = scratch + e.wp[i];
         hipLaunchKernelGGL(ew_pad_w_kernel, dim3(cdiv((long)Cp * g.k * Cp, 256)), dim3(256), 0, st, P[4 * i], wp, C, Cp, g.k);
         float* xh = saved + e.xhat[i];
-        hipLaunchKernelGGL(ew_gemm_kernel, dim3(cdiv(M, 128), Cp / 64, 1), dim3(256), 0, st, saved + e.y[i - 1], e.L[i - 1], g.k, g.s,
+        hipLaunchKernelGGL(ew_gemm_kernel<false>, dim3(cdiv(M, 128), Cp / 64, 1), dim3(256), 0, st, saved + e.y[i - 1], e.L[i - 1], g.k, g.s,
                            g.p, wp, 0L, P[4 * i + 1], xh, e.L[i], 1, 0, e.L[i], M, Cp, C);
         hipLaunchKernelGGL(ew_norm_fwd_kernel, dim3(cdiv(M, kEwNormRows)), dim3(256), 0, st, xh, P[4 * i + 2], P[4 * i + 3],
                            i < 4 ? saved + e.y[i] : z, i < 4 ? Cp : C, saved + e.rstd[i], M, C, Cp);
@@ -647,7 +677,7 @@ static int ew_backward(const float* wave, const float* const* P, const float* sa
         // the data gradient dy_{i-1}: one phase of input rows per z, every row u < L_{i-1} written
         const int V = (e.L[i - 1] + g.p + g.s - 1) / g.s;
         hipLaunchKernelGGL(ew_pad_wd_kernel, dim3(cdiv((long)g.s * Cp * 2 * Cp, 256)), dim3(256), 0, st, P[4 * i], wd, C, Cp, g.s);
-        hipLaunchKernelGGL(ew_gemm_kernel, dim3(cdiv((long)B * V, 128), Cp / 64, g.s), dim3(256), 0, st, dxb, e.L[i], 2, 1, 1, wd,
+        hipLaunchKernelGGL(ew_gemm_kernel<false>, dim3(cdiv((long)B * V, 128), Cp / 64, g.s), dim3(256), 0, st, dxb, e.L[i], 2, 1, 1, wd,
                            (long)Cp * 2 * Cp, (const float*)nullptr, dyb, e.L[i - 1], g.s, -g.p, V, (long)B * V, Cp, C);
         CPC_LAUNCH_CHECK();
     }
@@ -660,6 +690,528 @@ static int ew_backward(const float* wave, const float* const* P, const float* sa
     dst.stride[10] = dst.stride[11] = dst.stride[12] = 1;
     hipLaunchKernelGGL(ew_colsum_reduce_kernel, dim3(cdiv(13 * Cp, 256)), dim3(256), 0, st, part, e.nb_blocks[0], 13, Cp, C, dst);
     CPC_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------ normMode batchNorm / instanceNorm / ID
+// The same padded storage, GEMM, weight gradient and gather-form data gradient; the normalisation is per (group, channel), a group
+// being one utterance (instanceNorm: L_i rows) or the whole batch (batchNorm: B L_i rows).  A statistics pass writes centred
+// partials (mean, M2) per workgroup -- a workgroup's rows lie inside one group -- which a reduce combines in index order with
+// Chan's formula (never E[x^2] - E[x]^2); an apply pass writes xhat in place and y = relu(xhat w + b).  batchNorm in eval mode
+// takes mean and rstd from the running buffers and reduces nothing; ID has no statistics, no xhat and one elementwise ReLU pass.
+// conv0's output is never stored: the statistics, the apply pass and both backward passes form it again from the wave's ten taps.
+enum { kEnLayerNorm = 0, kEnBatchNorm = 1, kEnInstanceNorm = 2, kEnId = 3 };
+constexpr int kEnMaxBlocks = 1024;   // workgroups (= partial rows) of a column pass, at most, while a group has more than 64 rows
+
+// conv0's weights transposed into LDS: wt[tap][channel], zeros beyond C
+__device__ __forceinline__ void en_stage_w0(float* wt, const float* __restrict__ w0, int C, int Cp) {
+    for (int idx = threadIdx.x; idx < 10 * Cp; idx += 256) {
+        const int j = idx / Cp, c = idx - j * Cp;
+        wt[j * kEwMaxC + c] = c < C ? w0[c * 10 + j] : 0.f;
+    }
+    __syncthreads();
+}
+
+// Row m of a layer's conv + bias, channel lane + 64 q in v[q] (zero beyond C): formed from the wave's ten taps (kConv0; x keeps the
+// taps) or read from xin at pitch Cp
+template <bool kConv0>
+__device__ __forceinline__ void en_row(float (&v)[8], float (&x)[10], long m, const float* xin,
+                                       const float* __restrict__ wave, const float* wt, const float (&cb)[8], int L, int L0, int lane,
+                                       int nq, int C, int Cp) {
+    if (kConv0) {
+        const long b = m / L0;
+        const int t = (int)(m - b * L0);
+#pragma unroll
+        for (int j = 0; j < 10; ++j) {
+            const int pos = 5 * t - 3 + j;
+            x[j] = (pos >= 0 && pos < L) ? wave[b * L + pos] : 0.f;
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            float a = 0.f;
+            if (q < nq) {
+#pragma unroll
+                for (int j = 0; j < 10; ++j) a = fmaf(wt[j * kEwMaxC + lane + 64 * q], x[j], a);
+            }
+            // the bias last: one rounding at its magnitude, not ten -- a statistic's rstd (25 at layer 0) multiplies each of them
+            v[q] = a + cb[q];                               // zero beyond C: zero weights and bias
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = (q < nq && lane + 64 * q < C) ? xin[m * Cp + lane + 64 * q] : 0.f;
+    }
+}
+
+// the four waves' column sums -> part[slot][Cp], waves added in index order
+__device__ __forceinline__ void en_store_colsums(float* red, const float (&s)[8], long slot, float* __restrict__ part, int Cp) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 8; ++q) red[w * kEwMaxC + lane + 64 * q] = s[q];
+    __syncthreads();
+#pragma clang loop vectorize(disable) interleave(disable)
+    for (int c = threadIdx.x; c < Cp; c += 256)
+        part[slot * Cp + c] = ((red[c] + red[kEwMaxC + c]) + red[2 * kEwMaxC + c]) + red[3 * kEwMaxC + c];
+}
+
+// Statistics pass.  grid = (chunks, groups); the workgroup owns rows [blockIdx.x rows, + rows) of group blockIdx.y (Lg rows per
+// group).  Each wave runs Welford's update over its rows (every fourth), one channel per (lane, q); the four waves' (n, mean, M2) are
+// combined in index order with Chan's formula -> part[(group chunks + chunk) 2 + {0: mean, 1: M2}][Cp].  The count is the chunk's
+// row count, which the reduce knows from the shape.
+template <bool kConv0>
+__global__ __launch_bounds__(256) void en_stats_kernel(const float* __restrict__ xin, const float* __restrict__ wave,
+                                                       const float* __restrict__ w0, const float* __restrict__ b0,
+                                                       float* __restrict__ part, int L, int L0, int Lg, int rows, int C, int Cp) {
+    __shared__ float wt[10 * kEwMaxC];
+    float* red = wt;                                        // [wave][mean, M2][channel], once the rows are done
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nq = Cp >> 6;
+    float cb[8], mu[8], m2[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        cb[q] = (kConv0 && lane + 64 * q < C) ? b0[lane + 64 * q] : 0.f;
+        mu[q] = m2[q] = 0.f;
+    }
+    if (kConv0) en_stage_w0(wt, w0, C, Cp);
+    const int rb = blockIdx.x * rows;
+    const int re = rb + rows < Lg ? rb + rows : Lg;
+    const long base = (long)blockIdx.y * Lg;
+    int cnt = 0;
+    for (int r = rb + w; r < re; r += 4) {
+        float v[8], x[10];
+        en_row<kConv0>(v, x, base + r, xin, wave, wt, cb, L, L0, lane, nq, C, Cp);
+        const float inv = 1.0f / (float)(++cnt);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const float d = v[q] - mu[q];
+            mu[q] += d * inv;
+            m2[q] += d * (v[q] - mu[q]);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        red[(2 * w) * kEwMaxC + lane + 64 * q] = mu[q];
+        red[(2 * w + 1) * kEwMaxC + lane + 64 * q] = m2[q];
+    }
+    __syncthreads();
+    const int n = re - rb;                                  // >= 1; wave w saw (n - w + 3) / 4 rows
+    const long slot = ((long)blockIdx.y * gridDim.x + blockIdx.x) * 2;
+#pragma clang loop vectorize(disable) interleave(disable)
+    for (int c = threadIdx.x; c < Cp; c += 256) {
+        float na = (float)((n + 3) / 4), mean = red[c], M2 = red[kEwMaxC + c];
+        for (int ww = 1; ww < 4; ++ww) {
+            const int nw_ = (n - ww + 3) / 4;
+            if (nw_ <= 0) break;
+            const float nb = (float)nw_, nn = na + nb;
+            const float d = red[(2 * ww) * kEwMaxC + c] - mean;
+            mean += d * (nb / nn);
+            M2 += red[(2 * ww + 1) * kEwMaxC + c] + d * d * (na * nb / nn);
+            na = nn;
+        }
+        part[slot * Cp + c] = mean;
+        part[(slot + 1) * Cp + c] = M2;
+    }
+}
+
+// mean[g][c], rstd[g][c] (all Cp columns) from the chunks' partials, combined in index order with Chan's formula.  With run_mean
+// (batchNorm in training; one group) the running buffers are updated in place: the unbiased variance M2 / (n - 1) for running_var.
+__global__ __launch_bounds__(256) void en_stats_reduce_kernel(const float* __restrict__ part, float* __restrict__ mean_out,
+                                                              float* __restrict__ rstd_out, float* __restrict__ run_mean,
+                                                              float* __restrict__ run_var, float momentum, float eps, int groups,
+                                                              int chunks, int rows, int Lg, int C, int Cp) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= groups * Cp) return;
+    const int g = idx / Cp, c = idx - g * Cp;
+    const float* p = part + (long)g * chunks * 2 * Cp + c;
+    float na = (float)(rows < Lg ? rows : Lg), mean = p[0], M2 = p[Cp];
+    for (int k = 1; k < chunks; ++k) {
+        const int left = Lg - k * rows;
+        const float nb = (float)(left < rows ? left : rows), nn = na + nb;
+        const float d = p[(long)k * 2 * Cp] - mean;
+        mean += d * (nb / nn);
+        M2 += p[(long)k * 2 * Cp + Cp] + d * d * (na * nb / nn);
+        na = nn;
+    }
+    mean_out[idx] = mean;
+    rstd_out[idx] = 1.0f / sqrtf(M2 / (float)Lg + eps);
+    if (run_mean && c < C) {
+        run_mean[c] = (1.0f - momentum) * run_mean[c] + momentum * mean;
+        run_var[c] = (1.0f - momentum) * run_var[c] + momentum * (M2 / (float)(Lg - 1));
+    }
+}
+
+// batchNorm in eval mode: the statistics are the running buffers
+__global__ __launch_bounds__(256) void en_eval_stats_kernel(const float* __restrict__ run_mean, const float* __restrict__ run_var,
+                                                            float* __restrict__ mean_out, float* __restrict__ rstd_out, float eps,
+                                                            int C, int Cp) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= Cp) return;
+    mean_out[c] = c < C ? run_mean[c] : 0.f;
+    rstd_out[c] = c < C ? 1.0f / sqrtf(run_var[c] + eps) : 0.f;
+}
+
+// Apply pass: xhat = (x - mean[g]) rstd[g] written in place over x (layers 1..4; conv0 stores none), y = relu(xhat w + b) at pitch
+// ldy (Cp: zero pad columns; C: z).  mean == NULL is normMode ID: y = relu(x), x is left as it is.  One wave per row, the row's
+// group is m / Lg.
+template <bool kConv0>
+__global__ __launch_bounds__(256) void en_apply_kernel(float* __restrict__ xh, const float* __restrict__ wave,
+                                                       const float* __restrict__ w0, const float* __restrict__ b0,
+                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                       const float* __restrict__ nw, const float* __restrict__ nb,
+                                                       float* __restrict__ y, int ldy, int L, int L0, int Lg, long M, int C, int Cp) {
+    __shared__ float wt[kConv0 ? 10 * kEwMaxC : 1];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nq = Cp >> 6;
+    float gw[8], gb[8], cb[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int c = lane + 64 * q;
+        gw[q] = (mean && c < C) ? nw[c] : 1.f;
+        gb[q] = (mean && c < C) ? nb[c] : 0.f;
+        cb[q] = (kConv0 && c < C) ? b0[c] : 0.f;
+    }
+    if (kConv0) en_stage_w0(wt, w0, C, Cp);
+    for (int rr = 0; rr < kEwNormRows / 4; ++rr) {
+        const long m = (long)blockIdx.x * kEwNormRows + 4 * rr + w;
+        if (m >= M) break;                                  // wave-uniform
+        float v[8], x[10];
+        en_row<kConv0>(v, x, m, xh, wave, wt, cb, L, L0, lane, nq, C, Cp);
+        const long go = (m / Lg) * Cp;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int c = lane + 64 * q;
+            if (q < nq) {
+                const bool live = c < C;
+                float h = v[q];
+                if (mean) {
+                    h = live ? (v[q] - mean[go + c]) * rstd[go + c] : 0.f;
+                    if (!kConv0) xh[m * Cp + c] = h;
+                }
+                if (c < ldy) y[m * ldy + c] = live ? fmaxf(relu_in(h * gw[q] + gb[q]), 0.f) : 0.f;
+            }
+        }
+    }
+}
+
+// Backward, first pass: with g = dy [y > 0], the chunk's sums of g and of g xhat -> part[(group chunks + chunk) 2 + {0, 1}][Cp].
+// Summed over a group they are the two means the normalisation's gradient subtracts; summed over everything, the norm bias and
+// norm weight gradients.  grid = (chunks, groups), as the statistics pass.
+template <bool kConv0>
+__global__ __launch_bounds__(256) void en_bwd_sums_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ y, int ldy,
+                                                          const float* __restrict__ xh, const float* __restrict__ wave,
+                                                          const float* __restrict__ w0, const float* __restrict__ b0,
+                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                          float* __restrict__ part, int L, int L0, int Lg, int rows, int C, int Cp) {
+    __shared__ float wt[kConv0 ? 10 * kEwMaxC : 4 * kEwMaxC];
+    float* red = wt;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nq = Cp >> 6;
+    const long go = (long)blockIdx.y * Cp;
+    float cb[8], mu[8], rs[8], s1[8], s2[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int c = lane + 64 * q;
+        cb[q] = (kConv0 && c < C) ? b0[c] : 0.f;
+        mu[q] = (kConv0 && c < C) ? mean[go + c] : 0.f;
+        rs[q] = (kConv0 && c < C) ? rstd[go + c] : 0.f;
+        s1[q] = s2[q] = 0.f;
+    }
+    if (kConv0) en_stage_w0(wt, w0, C, Cp);
+    const int rb = blockIdx.x * rows;
+    const int re = rb + rows < Lg ? rb + rows : Lg;
+    const long base = (long)blockIdx.y * Lg;
+    for (int r = rb + w; r < re; r += 4) {
+        const long m = base + r;
+        float h[8], x[10];
+        en_row<kConv0>(h, x, m, xh, wave, wt, cb, L, L0, lane, nq, C, Cp);       // layers 1..4: xh holds xhat
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int c = lane + 64 * q;
+            const bool live = q < nq && c < C;
+            const float g = (live && y[m * ldy + c] > 0.f) ? dy[m * lddy + c] : 0.f;
+            const float hh = kConv0 ? (h[q] - mu[q]) * rs[q] : h[q];
+            s1[q] += g;
+            s2[q] += g * hh;
+        }
+    }
+    const long slot = ((long)blockIdx.y * gridDim.x + blockIdx.x) * 2;
+    en_store_colsums(red, s1, slot, part, Cp);
+    en_store_colsums(red, s2, slot + 1, part, Cp);
+}
+
+// sums[g][which][c] = the group's chunks in index order; the groups in index order are the norm bias (which 0) and norm weight
+// (which 1) gradients
+__global__ __launch_bounds__(256) void en_bwd_sums_reduce_kernel(const float* __restrict__ part, float* __restrict__ sums,
+                                                                 float* __restrict__ g_nb, float* __restrict__ g_nw, int groups,
+                                                                 int chunks, int C, int Cp) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= 2 * Cp) return;
+    const int which = idx / Cp, c = idx - which * Cp;
+    float total = 0.f;
+    for (int g = 0; g < groups; ++g) {
+        const float* p = part + ((long)g * chunks * 2 + which) * Cp + c;
+        float v = p[0];
+        for (int k = 1; k < chunks; ++k) v += p[(long)k * 2 * Cp];
+        sums[((long)g * 2 + which) * Cp + c] = v;
+        total = g ? total + v : v;
+    }
+    if (c < C) (which ? g_nw : g_nb)[c] = total;
+}
+
+// Backward, second pass: dx = a (g - s1 / n - xhat s2 / n), a = w rstd.  `subtract` == 0 (batchNorm in eval mode: an affine map)
+// drops the two means; mean == NULL (ID) is dx = g.  Layers 1..4 write dx at pitch Cp (zero pad columns) and the chunk's column sum
+// of dx -> part[block][Cp] (the conv bias gradient); conv0 writes no dx but part[block][0..9] = the ten taps of its weight
+// gradient and [10] = the conv bias.  grid = (chunks, groups).
+template <bool kConv0>
+__global__ __launch_bounds__(256) void en_bwd_dx_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ y, int ldy,
+                                                        const float* __restrict__ xh, const float* __restrict__ wave,
+                                                        const float* __restrict__ w0, const float* __restrict__ b0,
+                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                        const float* __restrict__ nw, const float* __restrict__ sums,
+                                                        float* __restrict__ dx, float* __restrict__ part, int L, int L0, int Lg,
+                                                        int rows, int C, int Cp, int subtract) {
+    __shared__ float wt[kConv0 ? 10 * kEwMaxC : 4 * kEwMaxC];
+    float* red = wt;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nq = Cp >> 6;
+    const long go = (long)blockIdx.y * Cp;
+    const float invn = 1.0f / (float)Lg;
+    float cb[8], mu[8], rs[8], a[8], s1n[8], s2n[8], s_cb[8], s_w[kConv0 ? 10 : 1][8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int c = lane + 64 * q;
+        const bool live = c < C;
+        cb[q] = (kConv0 && live) ? b0[c] : 0.f;
+        mu[q] = (mean && live) ? mean[go + c] : 0.f;
+        rs[q] = (mean && live) ? rstd[go + c] : 0.f;
+        a[q] = live ? (mean ? nw[c] * rs[q] : 1.f) : 0.f;
+        s1n[q] = (subtract && live) ? sums[2 * go + c] * invn : 0.f;
+        s2n[q] = (subtract && live) ? sums[2 * go + Cp + c] * invn : 0.f;
+        s_cb[q] = 0.f;
+#pragma unroll
+        for (int j = 0; j < (kConv0 ? 10 : 1); ++j) s_w[j][q] = 0.f;
+    }
+    if (kConv0) en_stage_w0(wt, w0, C, Cp);
+    const int rb = blockIdx.x * rows;
+    const int re = rb + rows < Lg ? rb + rows : Lg;
+    const long base = (long)blockIdx.y * Lg;
+    for (int r = rb + w; r < re; r += 4) {
+        const long m = base + r;
+        float h[8], x[10];
+        if (kConv0 || (mean && xh)) en_row<kConv0>(h, x, m, xh, wave, wt, cb, L, L0, lane, nq, C, Cp);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int c = lane + 64 * q;
+            const bool live = q < nq && c < C;
+            const float g = (live && y[m * ldy + c] > 0.f) ? dy[m * lddy + c] : 0.f;
+            const float hh = !mean ? 0.f : (kConv0 ? (h[q] - mu[q]) * rs[q] : h[q]);
+            const float d = live ? a[q] * (g - s1n[q] - hh * s2n[q]) : 0.f;
+            s_cb[q] += d;
+            if (kConv0) {
+#pragma unroll
+                for (int j = 0; j < 10; ++j) s_w[j][q] = fmaf(d, x[j], s_w[j][q]);
+            } else if (q < nq) {
+                dx[m * Cp + c] = d;
+            }
+        }
+    }
+    const long blk = (long)blockIdx.y * gridDim.x + blockIdx.x;
+    if (kConv0) {
+#pragma unroll
+        for (int j = 0; j < 10; ++j) en_store_colsums(red, s_w[j], blk * 11 + j, part, Cp);
+        en_store_colsums(red, s_cb, blk * 11 + 10, part, Cp);
+    } else {
+        en_store_colsums(red, s_cb, blk, part, Cp);
+    }
+}
+
+// ------------------------------------------------------------------ host side of the other normModes
+struct EnLayout {
+    EwLayout e;                                             // lengths, Cp, the weight gradients' row splits
+    int groups;                                             // statistic groups: B under instanceNorm, 1 otherwise
+    int Lg[5], rows[5], chunks[5];                          // rows per group, rows per workgroup, workgroups per group
+    long y[4], xhat[5], mean[5], rstd[5], saved_total;      // offsets (floats) into `saved`; ID keeps y0..y3 only
+    long wp[5], fpart, xtmp, fwd_total;                     // forward scratch
+    long wd, dxb, dyb, part, sums, bwd_total;               // backward scratch
+};
+
+static int en_layout(int B, int Lw, int C, int norm, int training, EnLayout& n) {
+    CPC_RETURN_IF(!ew_layout(B, Lw, C, n.e), CPC_ERR_SHAPE);
+    const EwLayout& e = n.e;
+    // the biased variance of one value is zero and torch refuses it: one utterance's last layer, the whole batch's in training
+    CPC_RETURN_IF(norm == kEnInstanceNorm && e.L[4] < 2, CPC_ERR_SHAPE);
+    CPC_RETURN_IF(norm == kEnBatchNorm && training && (long)B * e.L[4] < 2, CPC_ERR_SHAPE);
+    CPC_RETURN_IF(norm == kEnInstanceNorm && B > 65535, CPC_ERR_SHAPE);      // the groups are the grid's y
+    const int Cp = e.Cp;
+    const bool id = norm == kEnId;
+    n.groups = norm == kEnInstanceNorm ? B : 1;
+    long fpart = 0, part = 0;
+    for (int i = 0; i < 5; ++i) {
+        const long lg = norm == kEnInstanceNorm ? e.L[i] : (long)B * e.L[i];
+        long r = 64;
+        while (r < lg && n.groups * ((lg + r - 1) / r) > kEnMaxBlocks) r *= 2;
+        n.Lg[i] = (int)lg; n.rows[i] = (int)r; n.chunks[i] = (int)((lg + r - 1) / r);
+        const long blocks = (long)n.groups * n.chunks[i];
+        fpart = blocks * 2 * Cp > fpart ? blocks * 2 * Cp : fpart;
+        const long cols = blocks * (i ? 2 : 11) * Cp;
+        part = cols > part ? cols : part;
+        if (i) {
+            const long dw = (long)e.dw_splits[i] * Cp * kEwGeom[i].k * Cp;
+            part = dw > part ? dw : part;
+        }
+    }
+    long o = 0;
+    for (int i = 0; i < 4; ++i) { n.y[i] = o; o += ew_align((long)B * e.L[i] * Cp); }
+    n.xhat[0] = -1;
+    for (int i = 1; i < 5; ++i) { n.xhat[i] = id ? -1 : o; if (!id) o += ew_align((long)B * e.L[i] * Cp); }
+    for (int i = 0; i < 5; ++i) { n.mean[i] = id ? -1 : o; if (!id) o += ew_align((long)n.groups * Cp); }
+    for (int i = 0; i < 5; ++i) { n.rstd[i] = id ? -1 : o; if (!id) o += ew_align((long)n.groups * Cp); }
+    n.saved_total = o;
+
+    o = 0;
+    n.wp[0] = -1;
+    for (int i = 1; i < 5; ++i) { n.wp[i] = o; o += ew_align((long)Cp * kEwGeom[i].k * Cp); }
+    n.fpart = o; o += id ? 0 : ew_align(fpart);
+    n.xtmp = o; o += id ? ew_align((long)B * e.L[1] * Cp) : 0;      // ID: conv + bias of one layer, before its ReLU pass
+    n.fwd_total = o;
+
+    o = 0;
+    n.wd = o; o += ew_align((long)Cp * 8 * Cp);
+    n.dxb = o; o += ew_align((long)B * e.L[1] * Cp);
+    n.dyb = o; o += ew_align((long)B * e.L[0] * Cp);
+    n.part = o; o += ew_align(part);
+    n.sums = o; o += ew_align((long)n.groups * 2 * Cp);
+    n.bwd_total = o;
+    return 0;
+}
+
+static int en_check_params(const float* const* P, int norm) {
+    CPC_RETURN_IF(!P, CPC_ERR_ARG);
+    for (int q = 0; q < 20; ++q) CPC_RETURN_IF(!P[q] && !(norm == kEnId && (q & 2)), CPC_ERR_ARG);
+    return 0;
+}
+
+static int en_forward(const float* wave, const float* const* P, float* const* R, float* saved, float* scratch, float* z, int B, int L,
+                      int C, int norm, int training, float momentum, float eps, hipStream_t st) {
+    EnLayout n;
+    if (int rc = en_layout(B, L, C, norm, training, n)) return rc;
+    CPC_RETURN_IF(!wave || !saved || !scratch || !z || !ew_aligned16(saved) || !ew_aligned16(scratch), CPC_ERR_ARG);
+    if (int rc = en_check_params(P, norm)) return rc;
+    const bool bn = norm == kEnBatchNorm, id = norm == kEnId;
+    if (bn) {
+        CPC_RETURN_IF(!R, CPC_ERR_ARG);
+        for (int q = 0; q < 10; ++q) CPC_RETURN_IF(!R[q], CPC_ERR_ARG);
+    }
+    const EwLayout& e = n.e;
+    const int Cp = e.Cp;
+    const bool reduce = !id && !(bn && !training);          // batch statistics of this call
+    for (int i = 0; i < 5; ++i) {
+        const EwGeom g = kEwGeom[i];
+        const long M = (long)B * e.L[i];
+        float* xh = nullptr;
+        if (i) {
+            float* wp = scratch + n.wp[i];
+            xh = id ? scratch + n.xtmp : saved + n.xhat[i];
+            hipLaunchKernelGGL(ew_pad_w_kernel, dim3(cdiv((long)Cp * g.k * Cp, 256)), dim3(256), 0, st, P[4 * i], wp, C, Cp, g.k);
+            hipLaunchKernelGGL(ew_gemm_kernel<true>, dim3(cdiv(M, 128), Cp / 64, 1), dim3(256), 0, st, saved + n.y[i - 1], e.L[i - 1], g.k, g.s,
+                               g.p, wp, 0L, P[4 * i + 1], xh, e.L[i], 1, 0, e.L[i], M, Cp, C);
+            CPC_LAUNCH_CHECK();
+        }
+        float* mean = id ? nullptr : saved + n.mean[i];
+        float* rstd = id ? nullptr : saved + n.rstd[i];
+        if (reduce) {
+            float* part = scratch + n.fpart;
+            const dim3 grid(n.chunks[i], n.groups);
+            if (i) hipLaunchKernelGGL(en_stats_kernel<false>, grid, dim3(256), 0, st, xh, wave, P[0], P[1], part, L, e.L[0], n.Lg[i],
+                                      n.rows[i], C, Cp);
+            else hipLaunchKernelGGL(en_stats_kernel<true>, grid, dim3(256), 0, st, xh, wave, P[0], P[1], part, L, e.L[0], n.Lg[i],
+                                    n.rows[i], C, Cp);
+            hipLaunchKernelGGL(en_stats_reduce_kernel, dim3(cdiv((long)n.groups * Cp, 256)), dim3(256), 0, st, part, mean, rstd,
+                               bn ? R[2 * i] : (float*)nullptr, bn ? R[2 * i + 1] : (float*)nullptr, momentum, eps, n.groups,
+                               n.chunks[i], n.rows[i], n.Lg[i], C, Cp);
+        } else if (bn) {
+            hipLaunchKernelGGL(en_eval_stats_kernel, dim3(cdiv(Cp, 256)), dim3(256), 0, st, R[2 * i], R[2 * i + 1], mean, rstd, eps, C,
+                               Cp);
+        }
+        float* y = i < 4 ? saved + n.y[i] : z;
+        const int ldy = i < 4 ? Cp : C;
+        const float* nw = id ? nullptr : P[4 * i + 2];
+        const float* nb = id ? nullptr : P[4 * i + 3];
+        if (i) hipLaunchKernelGGL(en_apply_kernel<false>, dim3(cdiv(M, kEwNormRows)), dim3(256), 0, st, xh, wave, P[0], P[1], mean, rstd,
+                                  nw, nb, y, ldy, L, e.L[0], n.Lg[i], M, C, Cp);
+        else hipLaunchKernelGGL(en_apply_kernel<true>, dim3(cdiv(M, kEwNormRows)), dim3(256), 0, st, xh, wave, P[0], P[1], mean, rstd,
+                                nw, nb, y, ldy, L, e.L[0], n.Lg[i], M, C, Cp);
+        CPC_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+static int en_backward(const float* wave, const float* const* P, const float* saved, const float* z, const float* dz, float* scratch,
+                       float* const* G, int B, int L, int C, int norm, int training, hipStream_t st) {
+    EnLayout n;
+    if (int rc = en_layout(B, L, C, norm, training, n)) return rc;
+    CPC_RETURN_IF(!wave || !saved || !z || !dz || !scratch || !ew_aligned16(saved) || !ew_aligned16(scratch), CPC_ERR_ARG);
+    if (int rc = en_check_params(P, norm)) return rc;
+    if (int rc = en_check_params(G, norm)) return rc;
+    const bool id = norm == kEnId;
+    const int subtract = !id && !(norm == kEnBatchNorm && !training);
+    const EwLayout& e = n.e;
+    const int Cp = e.Cp;
+    float* wd = scratch + n.wd;
+    float* dxb = scratch + n.dxb;
+    float* dyb = scratch + n.dyb;
+    float* part = scratch + n.part;
+    float* sums = scratch + n.sums;
+    for (int i = 4; i >= 0; --i) {
+        const EwGeom g = kEwGeom[i];
+        const long M = (long)B * e.L[i];
+        const float* dy = i == 4 ? dz : dyb;
+        const float* y = i == 4 ? z : saved + n.y[i];
+        const int ld = i == 4 ? C : Cp;
+        const float* xh = (id || !i) ? nullptr : saved + n.xhat[i];
+        const float* mean = id ? nullptr : saved + n.mean[i];
+        const float* rstd = id ? nullptr : saved + n.rstd[i];
+        const dim3 grid(n.chunks[i], n.groups);
+        const int blocks = n.chunks[i] * n.groups;
+        if (!id) {
+            if (i) hipLaunchKernelGGL(en_bwd_sums_kernel<false>, grid, dim3(256), 0, st, dy, ld, y, ld, xh, wave, P[0], P[1], mean, rstd,
+                                      part, L, e.L[0], n.Lg[i], n.rows[i], C, Cp);
+            else hipLaunchKernelGGL(en_bwd_sums_kernel<true>, grid, dim3(256), 0, st, dy, ld, y, ld, xh, wave, P[0], P[1], mean, rstd,
+                                    part, L, e.L[0], n.Lg[i], n.rows[i], C, Cp);
+            hipLaunchKernelGGL(en_bwd_sums_reduce_kernel, dim3(cdiv(2 * Cp, 256)), dim3(256), 0, st, part, sums, G[4 * i + 3],
+                               G[4 * i + 2], n.groups, n.chunks[i], C, Cp);
+            CPC_LAUNCH_CHECK();
+        }
+        const float* nw = id ? nullptr : P[4 * i + 2];
+        EwColDst dst = {};
+        if (!i) {
+            hipLaunchKernelGGL(en_bwd_dx_kernel<true>, grid, dim3(256), 0, st, dy, ld, y, ld, xh, wave, P[0], P[1], mean, rstd, nw, sums,
+                               dxb, part, L, e.L[0], n.Lg[i], n.rows[i], C, Cp, subtract);
+            for (int j = 0; j < 10; ++j) { dst.p[j] = G[0] + j; dst.stride[j] = 10; }
+            dst.p[10] = G[1]; dst.stride[10] = 1;
+            hipLaunchKernelGGL(ew_colsum_reduce_kernel, dim3(cdiv(11 * Cp, 256)), dim3(256), 0, st, part, blocks, 11, Cp, C, dst);
+            CPC_LAUNCH_CHECK();
+            break;
+        }
+        hipLaunchKernelGGL(en_bwd_dx_kernel<false>, grid, dim3(256), 0, st, dy, ld, y, ld, xh, wave, P[0], P[1], mean, rstd, nw, sums,
+                           dxb, part, L, e.L[0], n.Lg[i], n.rows[i], C, Cp, subtract);
+        dst.p[0] = G[4 * i + 1]; dst.stride[0] = 1;
+        hipLaunchKernelGGL(ew_colsum_reduce_kernel, dim3(cdiv(Cp, 256)), dim3(256), 0, st, part, blocks, 1, Cp, C, dst);
+        CPC_LAUNCH_CHECK();
+        // the weight gradient and the data gradient dy_{i-1}, as under layerNorm
+        const int K = g.k * Cp;
+        hipLaunchKernelGGL(ew_wgrad_kernel, dim3(Cp / 64, K / 64, e.dw_splits[i]), dim3(256), 0, st, dxb, saved + n.y[i - 1], e.L[i - 1],
+                           e.L[i], g.s, g.p, part, M, Cp, K, e.dw_rows[i]);
+        hipLaunchKernelGGL(ew_dw_reduce_kernel, dim3(cdiv((long)C * C * g.k, 256)), dim3(256), 0, st, part, G[4 * i], C, Cp, g.k,
+                           e.dw_splits[i]);
+        CPC_LAUNCH_CHECK();
+        const int V = (e.L[i - 1] + g.p + g.s - 1) / g.s;
+        hipLaunchKernelGGL(ew_pad_wd_kernel, dim3(cdiv((long)g.s * Cp * 2 * Cp, 256)), dim3(256), 0, st, P[4 * i], wd, C, Cp, g.s);
+        hipLaunchKernelGGL(ew_gemm_kernel<false>, dim3(cdiv((long)B * V, 128), Cp / 64, g.s), dim3(256), 0, st, dxb, e.L[i], 2, 1, 1, wd,
+                           (long)Cp * 2 * Cp, (const float*)nullptr, dyb, e.L[i - 1], g.s, -g.p, V, (long)B * V, Cp, C);
+        CPC_LAUNCH_CHECK();
+    }
     return 0;
 }
 
@@ -706,6 +1258,61 @@ extern "C" int cpc_encoder_saved_activation_c(const float* saved, int layer, flo
     const long rows = (long)B * e.L[layer];
     hipLaunchKernelGGL(ew_unpad_kernel, dim3(cdiv(rows * C, 256)), dim3(256), 0, (hipStream_t)stream, saved + e.y[layer], dst, rows, C,
                        e.Cp);
+    CPC_LAUNCH_CHECK();
+    return 0;
+}
+
+// The encoder under any normMode: 0 layerNorm (the _c entries above: their kernels, launches and bits), 1 batchNorm,
+// 2 instanceNorm, 3 ID.  2 <= C <= 512 with 256 included: the 256-only kernels fuse ChannelNorm, so the other modes run 256 on the
+// padded path.  sizes has 32 slots: the first 22 as cpc_encoder_layout_c under layerNorm; otherwise 0..2 the totals, 3..7 L_i,
+// 8..11 y0..y3, 12..15 xhat1..4, 16..20 mean_i, 21..25 rstd_i (-1: not kept), 26 the row pitch, 27 the statistic groups.
+extern "C" int cpc_encoder_layout_n(int B, int L, int C, int norm, int training, long* sizes) {
+    CPC_RETURN_IF(norm < kEnLayerNorm || norm > kEnId, CPC_ERR_ARG);
+    if (norm == kEnLayerNorm) {
+        const int rc = cpc_encoder_layout_c(B, L, C, sizes);
+        if (rc == 0)
+            for (int i = 22; i < 32; ++i) sizes[i] = 0;
+        return rc;
+    }
+    EnLayout n;
+    if (int rc = en_layout(B, L, C, norm, training, n)) return rc;
+    CPC_RETURN_IF(!sizes, CPC_ERR_ARG);
+    for (int i = 0; i < 32; ++i) sizes[i] = 0;
+    sizes[0] = n.saved_total; sizes[1] = n.fwd_total; sizes[2] = n.bwd_total;
+    for (int i = 0; i < 5; ++i) sizes[3 + i] = n.e.L[i];
+    for (int i = 0; i < 4; ++i) sizes[8 + i] = n.y[i];
+    for (int i = 1; i < 5; ++i) sizes[11 + i] = n.xhat[i];
+    for (int i = 0; i < 5; ++i) { sizes[16 + i] = n.mean[i]; sizes[21 + i] = n.rstd[i]; }
+    sizes[26] = n.e.Cp; sizes[27] = n.groups;
+    return 0;
+}
+
+extern "C" int cpc_encoder_forward_n(const float* wave, const float* const* params, float* const* running, float* saved,
+                                     float* scratch, float* z, int B, int L, int C, int norm, int training, float momentum, float eps,
+                                     void* stream) {
+    CPC_RETURN_IF(norm < kEnLayerNorm || norm > kEnId, CPC_ERR_ARG);
+    if (norm == kEnLayerNorm) return cpc_encoder_forward_c(wave, params, saved, scratch, z, B, L, C, stream);
+    return en_forward(wave, params, running, saved, scratch, z, B, L, C, norm, training, momentum, eps, (hipStream_t)stream);
+}
+
+extern "C" int cpc_encoder_backward_n(const float* wave, const float* const* params, const float* saved, const float* z,
+                                      const float* dz, float* scratch, float* const* grads, int B, int L, int C, int norm,
+                                      int training, void* stream) {
+    CPC_RETURN_IF(norm < kEnLayerNorm || norm > kEnId, CPC_ERR_ARG);
+    if (norm == kEnLayerNorm) return cpc_encoder_backward_c(wave, params, saved, z, dz, scratch, grads, B, L, C, stream);
+    return en_backward(wave, params, saved, z, dz, scratch, grads, B, L, C, norm, training, (hipStream_t)stream);
+}
+
+extern "C" int cpc_encoder_saved_activation_n(const float* saved, int layer, float* dst, int B, int L, int C, int norm,
+                                              void* stream) {
+    CPC_RETURN_IF(norm < kEnLayerNorm || norm > kEnId, CPC_ERR_ARG);
+    if (norm == kEnLayerNorm) return cpc_encoder_saved_activation_c(saved, layer, dst, B, L, C, stream);
+    EnLayout n;
+    if (int rc = en_layout(B, L, C, norm, 0, n)) return rc;
+    CPC_RETURN_IF(!saved || !dst || layer < 0 || layer > 3, CPC_ERR_ARG);
+    const long rows = (long)B * n.e.L[layer];
+    hipLaunchKernelGGL(ew_unpad_kernel, dim3(cdiv(rows * C, 256)), dim3(256), 0, (hipStream_t)stream, saved + n.y[layer], dst, rows, C,
+                       n.e.Cp);
     CPC_LAUNCH_CHECK();
     return 0;
 }

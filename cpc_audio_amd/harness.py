@@ -499,7 +499,8 @@ def loadModel(pathCheckpoints, encoderKernel=False, hiddenKernel=False):
     call to call when samplingType is "sequential", as getAR builds it.  ``encoder_type`` 'lfb' and ``arMode`` 'no_ar' build LFBEnconder / NoAr
     (hiddenGar is then the encoder's width, cpc/train.py:486); 'mfcc' builds MFCCEncoder (build_model's mfccKernel).  Concatenated models -- more than one checkpoint at
     either level -- raise ValueError.  encoderKernel=True (default off) is build_model's: a CPCEncoder of another width than 256 on
-    the HIP kernels of any width.  hiddenKernel=True (default off) is build_model's too: a GRU checkpoint trained at another
+    the HIP kernels of any width, and a checkpoint of another ``normMode`` (read from the saved arguments: a batchNorm checkpoint
+    loads its (C,) weights and running statistics) on the kernels of that mode.  hiddenKernel=True (default off) is build_model's too: a GRU checkpoint trained at another
     hiddenGar than 256 opens on the GRU kernels of any hidden width (an LSTM checkpoint also needs lstmKernel, which this
     function does not take: it stays on torch)."""
     from .train import build_model
@@ -514,7 +515,7 @@ def loadModel(pathCheckpoints, encoderKernel=False, hiddenKernel=False):
                         keepHidden=saved.get("samplingType", "samespeaker") == "sequential",
                         reverse=saved.get("cpc_mode") == "reverse", arMode=arMode, sizeWindow=saved.get("sizeWindow", 20480),
                         abspos=saved.get("abspos", False), encoder_type=saved.get("encoder_type", "cpc"), mfccKernel=True,
-                        encoderKernel=encoderKernel, hiddenKernel=hiddenKernel)
+                        encoderKernel=encoderKernel, hiddenKernel=hiddenKernel, normMode=saved.get("normMode", "layerNorm"))
     print(f"Loading the state dict at {path}")
     model.load_state_dict(torch.load(path, map_location="cpu")["gEncoder"], strict=False)
     return model, hiddenGar, hiddenEncoder

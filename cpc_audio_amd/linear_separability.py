@@ -236,6 +236,9 @@ def parse_args(argv):
     # reference's namespace, which is also what checkpoint_args.json records)
     parser.add_argument('--wideKernel', action='store_true', default=argparse.SUPPRESS,
                         help="Run the classifier on the HIP kernels at feature widths other than 256 as well (1 to 512).")
+    parser.add_argument('--encoderKernel', action='store_true', default=argparse.SUPPRESS,
+                        help="The convolutional encoder on the HIP kernels at every width from 2 to 512 and under every normMode the checkpoint "
+                             "was trained with (off by default: 256 channels under layerNorm only, everything else on torch ops).")
     args = parser.parse_args(argv)
     if args.nGPU < 0:
         args.nGPU = 1
@@ -257,7 +260,8 @@ def main(argv):
     if len(args.load) == 0:
         raise ValueError("a checkpoint to evaluate is required")
     seqNames, speakers = findAllSeqs(args.pathDB, extension=args.file_extension, loadCache=not args.ignore_cache)
-    model, hidden_gar, _ = load_feature_maker(args.load[0], no_pretraining=args.no_pretraining)
+    model, hidden_gar, _ = load_feature_maker(args.load[0], no_pretraining=args.no_pretraining,
+                                             encoderKernel=getattr(args, "encoderKernel", False))
     hidden_encoder = model.gEncoder.getDimOutput()
     model.cuda()
     dim_features = hidden_encoder if args.get_encoded else hidden_gar

@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .ops import (EncoderFunction, EncoderWideFunction, GruFunction, GruHiddenFunction, LstmFunction, LstmHiddenFunction,
+from .ops import (EncoderFunction, EncoderNormFunction, EncoderWideFunction, GruFunction, GruHiddenFunction, LstmFunction, LstmHiddenFunction,
                   RnnFunction)
 
 
@@ -53,13 +53,20 @@ class CPCEncoder(nn.Module):
 
     conv{i} / batchNorm{i} carry the reference's names, shapes and default initialisation.  The configuration every BASELINE
     config and the reference's defaults use -- 256 channels, normMode 'layerNorm' (ChannelNorm) -- runs cpc_encoder_forward
-    (HIP, ``self.hip``); the reference's other options (``batchNorm`` / ``instanceNorm`` / ``ID``, other widths; cpc/model.py:
-    73-80) are served by the modules' own torch ops: correct on any device, differentiable, not the hot path.
+    (HIP, ``self.hip``); without the keyword below the reference's other options (``batchNorm`` / ``instanceNorm`` / ``ID``,
+    other widths; cpc/model.py:73-80) are served by the modules' own torch ops: correct on any device, differentiable.
 
     ``encoderKernel=True`` (an addition; default off) takes any other width from 2 to 512 under 'layerNorm' to the encoder kernels
     of any width for CUDA fp32 input (``self.hip_wide``; ops.EncoderWideFunction, cpc_encoder_forward_c / _backward_c: exact-f32
     MFMAs on zero-padded storage).  ``self.hip`` keeps meaning the 256 kernels -- what the fused train step tests -- and stays
-    False there; CPU input and other dtypes keep the torch ops.  Parameters, state-dict keys and shapes do not change."""
+    False there; CPU input and other dtypes keep the torch ops.  Parameters, state-dict keys and shapes do not change.
+    With the keyword the other three normModes run HIP kernels too (``self.hip_norm``; ops.EncoderNormFunction,
+    cpc_encoder_forward_n / _backward_n) at every width from 2 to 512, 256 included: nn.BatchNorm1d's batch
+    statistics and running buffers in training (``num_batches_tracked`` counted here, as a torch op) and its running statistics
+    in eval mode, nn.InstanceNorm1d's per-utterance statistics, ID's plain ReLU.  A window too short for torch's own check (one
+    value per channel), a BatchNorm1d whose ``momentum`` / ``eps`` / ``affine`` / ``track_running_stats`` were changed by hand,
+    CPU input and other dtypes keep the torch ops and raise where torch raises.  ``self.hip`` and ``self.hip_wide`` stay False for
+    these modes, so the fused one-call train step keeps declining such a model."""
 
     def __init__(self, sizeHidden=512, normMode="layerNorm", encoderKernel=False):
         super().__init__()
@@ -69,6 +76,8 @@ class CPCEncoder(nn.Module):
         self.hip = normMode == "layerNorm" and sizeHidden == 256
         self.hip_wide = (bool(encoderKernel) and normMode == "layerNorm" and sizeHidden != 256
                          and 2 <= sizeHidden <= ops.ENCODER_WIDE_MAX)
+        self.hip_norm = bool(encoderKernel) and normMode != "layerNorm" and 2 <= sizeHidden <= ops.ENCODER_WIDE_MAX
+        self.normMode = normMode
         if normMode == "instanceNorm":
             def normLayer(c): return nn.InstanceNorm1d(c, affine=True)
         elif normMode == "ID":
@@ -100,12 +109,50 @@ class CPCEncoder(nn.Module):
             out += [conv.weight, conv.bias, norm.weight, norm.bias]
         return out
 
+    def _norm_kernels_take(self, x):
+        """Do the kernels of the other normModes compute what the torch modules would for this input?  Not below torch's
+        minima (instanceNorm: two steps at the last layer; batchNorm in training: two values per channel), where torch raises,
+        and not for norm modules whose settings were changed by hand."""
+        if x.dim() != 3 or x.shape[1] != 1:
+            return False
+        lin = x.shape[2]
+        for k, s, p in ((10, 5, 3), (8, 4, 2), (4, 2, 1), (4, 2, 1), (4, 2, 1)):
+            if lin + 2 * p < k:
+                return False
+            lin = (lin + 2 * p - k) // s + 1
+        norms = [getattr(self, f"batchNorm{i}") for i in range(5)]
+        if self.normMode == "instanceNorm":
+            return lin >= 2 and all(n.affine and not n.track_running_stats and n.eps == 1e-5 for n in norms)
+        if self.normMode == "batchNorm":
+            return ((not self.training or x.shape[0] * lin >= 2) and
+                    all(n.affine and n.track_running_stats and n.momentum == 0.1 and n.eps == 1e-5
+                        and n.running_mean is not None and n.running_mean.dtype == torch.float32 for n in norms))
+        return True
+
+    def _forward_norm(self, x):
+        """z (B, L/160, C) on the kernels of batchNorm / instanceNorm / ID"""
+        norms = [getattr(self, f"batchNorm{i}") for i in range(5)]
+        running, training = None, self.training
+        if self.normMode == "batchNorm":
+            running = [t for n in norms for t in (n.running_mean, n.running_var)]
+            if training:
+                for n in norms:
+                    n.num_batches_tracked.add_(1)
+        if self.normMode == "ID":
+            params = [t for i in range(5) for t in (getattr(self, f"conv{i}").weight, getattr(self, f"conv{i}").bias)]
+        else:
+            params = self._flat_params()
+        return EncoderNormFunction.apply(x, self.normMode, training, running, 0.1, 1e-5, *params)
+
     def forward(self, x):
         """(B,1,L) -> (B,C,L/160), as the reference.  The kernels work channels-last, so the
         result is a (B,C,S) VIEW of a contiguous (B,S,C) tensor; CPCModel's permute(0,2,1)
         (model.py:287) therefore yields a contiguous (B,S,C) z at no cost."""
         if self.hip_wide and x.is_cuda and x.dtype == torch.float32 and self.conv0.weight.dtype == torch.float32:
             return EncoderWideFunction.apply(x, *self._flat_params()).permute(0, 2, 1)
+        if self.hip_norm and x.is_cuda and x.dtype == torch.float32 and self.conv0.weight.dtype == torch.float32 \
+                and self._norm_kernels_take(x):
+            return self._forward_norm(x).permute(0, 2, 1)
         if not self.hip:
             for i in range(5):                                 # cpc/model.py:99-105 with the modules' own torch ops
                 x = torch.relu(getattr(self, f"batchNorm{i}")(getattr(self, f"conv{i}")(x)))

@@ -473,6 +473,69 @@ class EncoderWideFunction(torch.autograd.Function):
         return (None, *grads)
 
 
+ENCODER_NORM_CODES = {"layerNorm": 0, "batchNorm": 1, "instanceNorm": 2, "ID": 3}      # `norm` of the cpc_encoder_*_n entries
+
+
+class EncoderNormFunction(torch.autograd.Function):
+    """wave (B,1,L), normMode, training, the ten running buffers (batchNorm: running_mean / running_var of layers 0..4; None
+    otherwise), momentum, eps + the encoder parameters in state-dict order -> z (B, L/160, C), contiguous: cpc_encoder_forward_n /
+    _backward_n (csrc/enc_wide.hip), 2 <= C <= 512.  The parameters are 20 under batchNorm / instanceNorm (norm weight
+    and bias of shape (C,)) and the 10 conv tensors under ID.  A plain autograd node on the current stream, as
+    EncoderWideFunction.  Under batchNorm in training the running buffers are updated in place by the forward call, once, outside
+    the graph; num_batches_tracked is the module's to count.  The wave receives no gradient."""
+
+    @staticmethod
+    def forward(ctx, wave, normMode, training, running, momentum, eps, *params):
+        _require_cuda(wave, "EncoderNormFunction")
+        lib = _lib.get()
+        B, ch, L = wave.shape
+        norm = ENCODER_NORM_CODES[normMode]
+        ident = normMode == "ID"
+        if ch != 1 or norm == 0 or len(params) != (10 if ident else 20):
+            raise ValueError("EncoderNormFunction expects (B,1,L) waveforms, normMode batchNorm / instanceNorm / ID and the "
+                             "encoder's parameters in state-dict order")
+        C = params[0].shape[0]
+        want = []
+        for i, k in enumerate((10, 8, 4, 4, 4)):
+            want += [(C, 1 if i == 0 else C, k), (C,)] + ([] if ident else [(C,), (C,)])
+        if not 2 <= C <= ENCODER_WIDE_MAX or [tuple(p.shape) for p in params] != want:
+            raise NotImplementedError(f"cpc_audio_amd.EncoderNormFunction: 2 <= sizeHidden <= {ENCODER_WIDE_MAX} and the "
+                                      f"reference's parameter shapes expected (conv0.weight {tuple(params[0].shape)})")
+        if normMode == "batchNorm" and (running is None or len(running) != 10 or any(
+                r.shape != (C,) or r.dtype != torch.float32 or not r.is_contiguous() or r.device != wave.device for r in running)):
+            raise ValueError("EncoderNormFunction: batchNorm needs the ten (C,) fp32 running buffers on the wave's device")
+        wave = wave.contiguous()
+        params = [p.detach().contiguous() for p in params]
+        slots = params if not ident else [t for i in range(5) for t in (params[2 * i], params[2 * i + 1], None, None)]
+        training = 1 if training else 0
+        with torch.cuda.device(wave.device):
+            sizes = _layout("encoder_layout_n", lib.cpc_encoder_layout_n, 32, B, L, C, norm, training)
+            saved = torch.empty(max(1, sizes[0]), device=wave.device, dtype=torch.float32)
+            scratch = torch.empty(max(1, sizes[1]), device=wave.device, dtype=torch.float32)
+            z = torch.empty(B, sizes[7], C, device=wave.device, dtype=torch.float32)
+            lib.check(lib.cpc_encoder_forward_n(_p(wave), _ptrs(slots), _ptrs(list(running)) if normMode == "batchNorm" else None,
+                                                _p(saved), _p(scratch), _p(z), B, L, C, norm, training, float(momentum), float(eps),
+                                                _stream()), "encoder_forward_n")
+        ctx.save_for_backward(wave, saved, z, *params)
+        ctx.dims = (B, L, C, norm, training, sizes[2])
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        lib = _lib.get()
+        wave, saved, z, *params = ctx.saved_tensors
+        B, L, C, norm, training, nscr = ctx.dims
+        ident = norm == ENCODER_NORM_CODES["ID"]
+        dz = dz.contiguous()
+        with torch.cuda.device(wave.device):
+            scratch = torch.empty(nscr, device=wave.device, dtype=torch.float32)
+            grads = [torch.empty_like(p) for p in params]
+            pad = (lambda ts: ts) if not ident else (lambda ts: [t for i in range(5) for t in (ts[2 * i], ts[2 * i + 1], None, None)])
+            lib.check(lib.cpc_encoder_backward_n(_p(wave), _ptrs(pad(params)), _p(saved), _p(z), _p(dz), _p(scratch),
+                                                 _ptrs(pad(grads)), B, L, C, norm, training, _stream()), "encoder_backward_n")
+        return (None, None, None, None, None, None, *grads)
+
+
 IN_PROJ_MAX = 512      # widest layer-0 input of the recurrent cells (cpc_*_in; csrc/in_proj.hip)
 LSTM_HIDDEN_MAX = 512  # widest hidden state of the LSTM at any hidden width (cpc_lstm_*_h; csrc/lstm.hip)
 

@@ -13,7 +13,7 @@ from .optim import Adam
 
 def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False, reverse=False, arMode="GRU",
                 sizeWindow=20480, abspos=False, transformerDropout=0.1, lstmKernel=False, encoder_type="cpc", rnnKernel=False,
-                mfccKernel=False, inputKernel=False, hiddenKernel=False, encoderKernel=False):
+                mfccKernel=False, inputKernel=False, hiddenKernel=False, encoderKernel=False, normMode="layerNorm"):
     """cpc/feature_loader.py:124-153 (getEncoder / getAR) + cpc/train.py:311.  arMode 'GRU' (north star) or
     'transformer' (BASELINE.json config 4: buildTransformerAR(hiddenEncoder, 1, sizeWindow // 160, abspos)); 'LSTM' /
     'RNN' as the reference (lstmKernel / rnnKernel: the LSTM / the RNN on the HIP kernels, CPCAR); 'no_ar': the identity, and the context width is
@@ -25,7 +25,9 @@ def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False
     hiddenKernel=True (default off likewise): a hiddenGar in 1..512 other than 256 runs the recurrence kernels of any hidden
     width -- arMode 'GRU' with nothing else (CPCAR.hip_gru_hidden), arMode 'LSTM' with lstmKernel (CPCAR.hip_hidden); the RNN at
     such a width stays on torch.  encoderKernel=True (default off likewise; encoder_type 'cpc'): a
-    hiddenEncoder in 2..512 other than 256 runs the encoder kernels of any width (CPCEncoder.hip_wide)."""
+    hiddenEncoder in 2..512 other than 256 runs the encoder kernels of any width (CPCEncoder.hip_wide).  normMode is the
+    reference's --normMode ('layerNorm', 'batchNorm', 'instanceNorm', 'ID'; encoder_type 'cpc'); with encoderKernel=True the
+    other three run the HIP kernels too, at any hiddenEncoder in 2..512 (CPCEncoder.hip_norm)."""
     if encoder_type == "mfcc" and not mfccKernel:
         raise NotImplementedError("encoder_type 'mfcc' is torchaudio.transforms.MFCC in the reference; torchaudio is not a "
                                   "dependency of this package.  Pass mfccKernel=True for MFCCEncoder, the package's own "
@@ -35,7 +37,7 @@ def build_model(hiddenEncoder=256, hiddenGar=256, nLevelsGRU=2, keepHidden=False
     if encoder_type == "mfcc":
         enc = MFCCEncoder(hiddenEncoder)
     else:
-        enc = LFBEnconder(hiddenEncoder) if encoder_type == "lfb" else CPCEncoder(hiddenEncoder, "layerNorm",
+        enc = LFBEnconder(hiddenEncoder) if encoder_type == "lfb" else CPCEncoder(hiddenEncoder, normMode,
                                                                                              encoderKernel=encoderKernel)
     if arMode == "no_ar":
         ar = NoAr()

@@ -279,6 +279,28 @@ int cpc_encoder_backward_c(const float* wave, const float* const* params, const 
 /* dst (B,L_layer,C), the true width: the saved output of layer `layer` (0..3) of a cpc_encoder_forward_c.  Tests / debugging. */
 int cpc_encoder_saved_activation_c(const float* saved, int layer, float* dst, int B, int L, int C, void* stream);
 
+/* The encoder at C channels under any of the reference's normModes (csrc/enc_wide.hip).  norm: 0 layerNorm (forwards
+ * to the _c entries above: their kernels, launches and bits), 1 batchNorm (nn.BatchNorm1d), 2 instanceNorm (nn.InstanceNorm1d with
+ * affine parameters, the same in train and eval), 3 ID (relu(conv + bias)); any other value: CPC_ERR_ARG.  2 <= C <= 512, 256
+ * included (the other modes run it on the padded storage).  params / grads keep 20 slots in state-dict order; norm weight and
+ * bias are read as C contiguous floats (the (C,) of the torch modules; ChannelNorm's (1,C,1) under layerNorm); under ID the norm
+ * slots may be NULL and are not touched.  running: 10 pointers, running_mean and running_var of layers 0..4 in that order --
+ * required under batchNorm (CPC_ERR_ARG when NULL), read in eval mode, and in training updated in place once per forward call:
+ * mean with `momentum`, var with the unbiased batch variance.  instanceNorm needs L_4 >= 2 and B <= 65535, batchNorm in training B L_4 >= 2:
+ * CPC_ERR_SHAPE otherwise, as for a shape the _c entries refuse.  cpc_encoder_layout_n fills 32 slots: under layerNorm the 22 of
+ * cpc_encoder_layout_c; otherwise 0..2 the float counts of saved / forward scratch / backward scratch, 3..7 L_0..L_4, 8..11 the
+ * offsets of y0..y3 in `saved`, 12..15 xhat1..4, 16..20 mean per layer, 21..25 rstd per layer ((groups, pitch) each; -1 under
+ * ID, which keeps y0..y3 only), 26 the row pitch 64 ceil(C / 64), 27 the statistic groups (B under instanceNorm, else 1).
+ * `training` must be the same in the three calls.  The statistics use centred partials combined in index order (no atomics, no
+ * E[x^2] - E[x]^2): two calls give the same bits.  Every gradient, z and every saved tensor the backward reads are fully overwritten. */
+int cpc_encoder_layout_n(int B, int L, int C, int norm, int training, long* sizes);
+int cpc_encoder_forward_n(const float* wave, const float* const* params, float* const* running, float* saved, float* scratch,
+                          float* z, int B, int L, int C, int norm, int training, float momentum, float eps, void* stream);
+int cpc_encoder_backward_n(const float* wave, const float* const* params, const float* saved, const float* z, const float* dz,
+                           float* scratch, float* const* grads, int B, int L, int C, int norm, int training, void* stream);
+/* dst (B,L_layer,C): the saved output of layer `layer` (0..3) of a cpc_encoder_forward_n.  Tests / debugging. */
+int cpc_encoder_saved_activation_n(const float* saved, int layer, float* dst, int B, int L, int C, int norm, void* stream);
+
 /* ------------------------------------------------------------ plain GEMMs ----
  * C[M,N] = A[M,K] . B[N,K]^T + bias[N]   (N % 128 == 0, K % 16 == 0; bias may be NULL).
  * This is torch.nn.Linear's arithmetic (criterion.py:90-91,108; the GRU projections). */
